@@ -17,7 +17,15 @@ host-driven loop (K x (policy -> rv_set_actions -> rv_step_macro -> rv_observe w
 point cloud -> rv_reward), every env waiting for the slowest env of each step) is
 reported beside it as "lockstep_env_step" (or is `value` with --mode lockstep).
 
+A plain run sets up, warms up, times the --steps steps and prints the result line.
+Everything else -- the extra GPU legs (K = 50, lock-step, partial batches, async,
+configs 3 / 4 / 5, the semantics legs), the CPU-oracle baselines, the FP32-vs-FP64
+pose error and the pybullet probe, and the full record in bench_legs.json -- runs
+with --full.  --dump-outputs DIR writes the observation, reward and done of the
+last timed step as DIR/<name>.npy (float32 / float64).
+
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \\
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 """
@@ -37,6 +45,7 @@ HBM_PEAK_GBS = 8000.0               # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 VALU_PEAK_PER_SIMD_CYCLE = 0.5      # MI355X_MICROARCH.md: a wave64 VALU instruction issues over 2 cycles on a SIMD-32
 
 LINE_LIMIT = 8000                   # bytes of the ONE stdout line (the round-5 line was 22.7 KB and the driver could not parse it)
+DUMP_LIMIT = 64 * 10 ** 6          # bytes written by --dump-outputs, all ranks together
 
 
 def _short(s, n=220):
@@ -140,6 +149,32 @@ def compact_line(full, limit=LINE_LIMIT, full_record=None):
         text = json.dumps(_sig(line))
     assert len(text) < limit, len(text)
     return text
+
+
+def dump_outputs(out_dir, obs, reward, done, rank=0, world_size=1):
+    """What the timed path returned for its last step -- observation dict, reward, done; tensors or arrays of one
+    rank's envs -- as <out_dir>/<name>.npy: float32, integer fields as float64 (exact).  Above this rank's share of
+    DUMP_LIMIT a fixed, seeded sample of the envs is written, and their global env ids as env_index.npy."""
+    import numpy as np
+
+    def host(x):
+        return x.cpu().numpy() if hasattr(x, 'cpu') else np.asarray(x)
+    arrays = {'obs_' + k: host(v) for k, v in obs.items()}
+    arrays['reward'], arrays['done'] = host(reward), host(done)
+    arrays = {k: v.astype(np.float64 if v.dtype == np.int64 else np.float32) for k, v in arrays.items()}
+    n_envs = arrays['reward'].shape[0]
+    per_env = sum(v.nbytes for v in arrays.values()) // n_envs
+    limit = DUMP_LIMIT // world_size
+    if per_env * n_envs > limit:
+        # (room for the env ids and a 128-byte header per file)
+        keep = (limit - 128 * (len(arrays) + 1)) // (per_env + 8)
+        idx = np.sort(np.random.default_rng(0).choice(n_envs, keep, replace=False))
+        arrays = {k: v[idx] for k, v in arrays.items()}
+        arrays['env_index'] = (idx + rank * n_envs).astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = '' if world_size == 1 else '_rank%d' % rank
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + suffix + '.npy'), v)
 
 
 def effective_cpus():
@@ -371,6 +406,11 @@ def main():
     ap.add_argument('--envs-per-gpu', type=int, default=None,
                     help='default: 1024 at --gpus 1 (BASELINE configs[1]), 8192 at --gpus N > 1 (BASELINE configs[4])')
     ap.add_argument('--seed', type=int, default=1234)
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline, run the extra GPU legs, the CPU-oracle legs and the pose-error leg, and write the '
+                         'full record (--legs-out); the options below that skip or add legs apply to such a run')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the timed path returned for its last step (observation, reward, done) as DIR/<name>.npy')
     ap.add_argument('--no-cpu-baseline', action='store_true', help='skip every CPU-oracle leg')
     ap.add_argument('--no-extra-legs', action='store_true',
                     help='only the headline: skip lockstep_env_step, async_rollout, config3_4096, config5_8192')
@@ -388,7 +428,9 @@ def main():
     ap.add_argument('--extra-legs', action='store_true', help='run the extra legs at --gpus N > 1 as well (default: N = 1 only -- '
                     'at 8192 envs per rank the no-deactivation legs alone take minutes)')
     args = ap.parse_args()
-    headline_only_run = args.no_extra_legs or args.workload != 'config2' or bool(args.over)      # (asked for on the command line: a profiling run)
+    if not args.full:
+        args.no_cpu_baseline = args.no_extra_legs = True
+    headline_only_run = args.no_extra_legs or args.workload != 'config2' or bool(args.over)      # (without --full, or a profiling run)
     if args.gpus > 1 and not args.extra_legs:
         args.no_extra_legs = True
 
@@ -509,7 +551,8 @@ def main():
         return float(t.item())
 
     def time_rollout(world, k_steps, first):
-        """K env.step() per env in one launch, every step's observation recorded."""
+        """K env.step() per env in one launch, every step's observation recorded.  Also returns the
+        observation, reward and done of the last step."""
         barrier()
         t0 = time.perf_counter()
         obs, r, d = world.rollout_record(k_steps, first_macro_index=first, auto_reset=True, point_cloud=True)
@@ -517,14 +560,15 @@ def main():
         st = world.stats()
         barrier()
         el = all_max(time.perf_counter() - t0)
-        return el, st, world.last_kernel_ms(), 1
+        return el, st, world.last_kernel_ms(), 1, ({k: v[-1] for k, v in obs.items()}, r[-1], d[-1])
 
     def time_lockstep(world, k_steps, first):
         barrier()
         t0 = time.perf_counter()
         kern_ms, tot = 0.0, {'substeps': 0, 'env_steps': 0, 'max_substeps': 0, 'awake_substeps': 0}
+        last = None
         for k in range(k_steps):
-            lockstep_step(world, first + k)
+            last = lockstep_step(world, first + k)
             st = world.stats()     # synchronises, as a Python env loop that reads rewards does
             kern_ms += world.last_kernel_ms()
             for key in ('substeps', 'env_steps', 'awake_substeps'):
@@ -532,7 +576,7 @@ def main():
             tot['max_substeps'] = max(tot['max_substeps'], st['max_substeps'])
         barrier()
         el = all_max(time.perf_counter() - t0)
-        return el, tot, kern_ms, k_steps
+        return el, tot, kern_ms, k_steps, last
 
     # ---- semantics legs: the same workload / seed / actions under other physics settings -------------------
     # What the reference most likely runs (RECALLED PyBullet behaviour, DESIGN.md section 3, table of recalled
@@ -625,7 +669,10 @@ def main():
         first_timed = args.warmup + args.steps
     else:
         first_timed = args.warmup
-    elapsed, st, kern_ms, launches = timer(world, args.steps, first_timed)
+    elapsed, st, kern_ms, launches, last_step = timer(world, args.steps, first_timed)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, *last_step, rank=rank, world_size=world_size)
+    del last_step
     env_steps_all, substeps_all = all_sum(st['env_steps'], st['substeps'])
     next_index = first_timed + args.steps
 
@@ -634,11 +681,11 @@ def main():
         extra['dist_note'] = dist_note
     if not args.no_extra_legs:
         # BASELINE.md's config 2 names 50 macro-steps per env: the same single-launch rollout with K = 50
-        el50, st50, km50, _ = time_rollout(world, 50, next_index); next_index += 50
+        el50, st50, km50, _, _ = time_rollout(world, 50, next_index); next_index += 50
         extra['config2_k50'] = leg_summary(el50, st50, 50, n)
         extra['config2_k50'].update({'kernel_ms': km50, 'roofline_frac_nominal': ALGO_BYTES['config2'] * st50['substeps'] / (1e-3 * km50) / 1e9 / HBM_PEAK_GBS})
         other = time_lockstep if args.mode == 'rollout' else time_rollout
-        el2, st2, km2, _ = other(world, args.steps, next_index); next_index += args.steps
+        el2, st2, km2, _, _ = other(world, args.steps, next_index); next_index += args.steps
         name = 'lockstep_env_step' if args.mode == 'rollout' else 'single_launch_rollout'
         extra[name] = leg_summary(el2, st2, args.steps, n)
         extra[name]['kernel_ms_per_step'] = km2 / args.steps
@@ -714,7 +761,7 @@ def main():
         w3, _ = make_world(4096, TASK_NAME='crossing', LAYOUT_ID=0, MOVABLE_NAME='CONCAVE', MAX_STEPS=10)
         w3.reset()
         k3 = min(args.steps, 10)
-        el3, st3, km3, _ = time_rollout(w3, k3, 0)
+        el3, st3, km3, _, _ = time_rollout(w3, k3, 0)
         extra['config3_4096'] = leg_summary(el3, st3, k3, 4096)
         extra['config3_4096'].update({'workload': "PushEnv 'crossing' layout 0, V-HACD concave movables, PushReward, MAX_STEPS=10",
                                       'roofline_frac_nominal': ALGO_BYTES['config3'] * st3['substeps'] / (1e-3 * km3) / 1e9 / HBM_PEAK_GBS})
@@ -725,7 +772,7 @@ def main():
         w5, _ = make_world(8192)
         w5.reset()
         w5.rollout(args.warmup, first_macro_index=0, auto_reset=True, record=True)
-        el5, st5, km5, _ = time_rollout(w5, args.steps, args.warmup)
+        el5, st5, km5, _, _ = time_rollout(w5, args.steps, args.warmup)
         extra['config5_8192'] = leg_summary(el5, st5, args.steps, 8192)
         extra['config5_8192'].update({'workload': 'config-2 scene, 8192 envs per GPU, %d steps after %d warm-up steps (task queue: one env.step() per task)' % (args.steps, args.warmup),
                                       'roofline_frac_nominal': ALGO_BYTES['config2'] * st5['substeps'] / (1e-3 * km5) / 1e9 / HBM_PEAK_GBS})
@@ -999,7 +1046,9 @@ def main():
             legs_path = 'not written: %r' % (ex,)
         sys.stderr.write('bench.py full record: ' + json.dumps(out) + '\n')
         sys.stderr.flush()
-        os.write(json_fd, (compact_line(out, full_record=os.path.basename(legs_path) if os.path.sep in legs_path else legs_path) + '\n').encode())
+        written = legs_path == args.legs_out
+        full_record = (os.path.basename(legs_path) if written else legs_path) if (written or args.full) else None
+        os.write(json_fd, (compact_line(out, full_record=full_record) + '\n').encode())
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()

@@ -5,7 +5,7 @@
 # Stages:
 #   tests          pytest -m gpu (whole suite) + smoke()
 #   tests:<expr>   pytest -m gpu -k <expr>
-#   bench          the driver's command: python bench.py --steps 20 --warmup 5
+#   bench          every leg and the full record: python bench.py --steps 20 --warmup 5 --full
 #   qstress / qstress50   tools/queue_stress.py 16 / 50 runs (task queues vs plain launch, every word)
 #   c5             bench.py --workload config5 alone
 #   headline       bench.py headline only (no CPU legs, no extra legs)
@@ -34,7 +34,7 @@ for STAGE in "$@"; do
       timeout 1500 python -m pytest tests -m gpu -x -q -k "${STAGE#tests:}" > $O/tests_k.log 2>&1; echo "tests -k rc=$?" >> $O/time.txt
       tail -5 $O/tests_k.log ;;
     bench)
-      timeout 1700 python bench.py --steps 20 --warmup 5 --legs-out $O/bench_legs.json > $O/bench.json 2> $O/bench.err; echo "bench rc=$?" >> $O/time.txt
+      timeout 1700 python bench.py --steps 20 --warmup 5 --full --legs-out $O/bench_legs.json > $O/bench.json 2> $O/bench.err; echo "bench rc=$?" >> $O/time.txt
       python tools/bench_digest.py $O/bench.json ;;
     qstress)
       timeout 1500 python tools/queue_stress.py 16 > $O/queue_stress.txt 2>&1; echo "qstress rc=$?" >> $O/time.txt; tail -4 $O/queue_stress.txt ;;
