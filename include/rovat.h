@@ -387,6 +387,50 @@ int  rv_policy_random(rv_world* w, int32_t macro_index, float* d_actions);
  *      (push_policy.py:33-52, heuristic_push_sampler.py:66-123). ---- */
 int  rv_policy_heuristic(rv_world* w, int32_t max_attempts, float* d_actions);
 
+/* ---- AntipodalGrasp4DofPolicy._action (grasp_policy.py:17-75) over
+ *      AntipodalDepthImageGraspSampler._sample(depth, intrinsics, 1)
+ *      (image_grasp_sampler.py:149-375), one grasp per env; the semantics and
+ *      the departures are written out in csrc/rv_dev_grasp_sampler.h. ---- */
+#define RV_AP_MAX_RADIUS  32    /* Gaussian radius int(4 sigma + 0.5) <= 32 (sigma < 7.875) */
+#define RV_AP_MAX_EDGES 4096    /* edge pixels one env may have (LDS: 12 B each)            */
+#define RV_AP_OK              1 /* status per env: a grasp                                  */
+#define RV_AP_NO_EDGES        0 /*   no edge pixel                                          */
+#define RV_AP_NO_PAIRS      (-1)/*   no valid (antipodal, narrow enough) pair               */
+#define RV_AP_ALL_REJECTED  (-2)/*   'Failed to sample any valid grasp.' (:359-360)          */
+#define RV_AP_TOO_MANY_EDGES (-3)/*  more than RV_AP_MAX_EDGES edge pixels (never truncated) */
+typedef struct rv_antipodal_params {
+  /* config.SAMPLER (grasp_policy.py:30-46) */
+  float   friction_coef;               /* FRICTION_COEF                                      */
+  float   depth_grad_thresh;           /* DEPTH_GRAD_THRESH                                  */
+  float   depth_grad_gaussian_sigma;   /* DEPTH_GRAD_GAUSSIAN_SIGMA                          */
+  int32_t downsample_rate;             /* DOWNSAMPLE_RATE, 1..8                              */
+  int32_t max_rejection_samples;       /* MAX_REJECTION_SAMPLES, >= 1                        */
+  int32_t use_crop;                    /* 0: CROP = None (the whole image)                   */
+  int32_t crop[4];                     /* CROP = [r0, c0, r1, c1]                            */
+  float   min_dist_from_boundary;      /* MIN_DIST_FROM_BOUNDARY > max(WH, WW)               */
+  float   min_grasp_dist;              /* MIN_GRASP_DIST (unused: one grasp per env)          */
+  float   angle_dist_weight;           /* ANGLE_DIST_WEIGHT (unused: one grasp per env)       */
+  int32_t depth_samples_per_grasp;     /* DEPTH_SAMPLES_PER_GRASP, must be 1                 */
+  float   min_depth_offset;            /* MIN_DEPTH_OFFSET                                   */
+  float   max_depth_offset;            /* MAX_DEPTH_OFFSET                                   */
+  float   depth_sample_window_height;  /* DEPTH_SAMPLE_WINDOW_HEIGHT (WH), >= 1              */
+  float   depth_sample_window_width;   /* DEPTH_SAMPLE_WINDOW_WIDTH (WW), >= 1               */
+  /* config.GRIPPER_WIDTH (grasp_policy.py:47), metres; <= 0: no width limit */
+  float   gripper_width;
+  /* computed on the host in float64 and rounded to float32 */
+  float   cone_cos;                    /* cos(arctan(FRICTION_COEF))                         */
+  int32_t gauss_radius;                /* int(4 sigma + 0.5), 0 when sigma <= 1e-15          */
+  float   gauss_weights[RV_AP_MAX_RADIUS + 1]; /* w[k], k = 0..radius: exp(-k^2 / 2 sigma^2), normalised over -radius..radius */
+} rv_antipodal_params;
+/* d_depth: [N][H][W] eye-z depth (0 = nothing hit), NULL = rv_render it now.
+ * d_image_grasps [N][5]: [x1, y1, x2, y2, depth] in image pixels.  d_actions4 [N][4] (or NULL): the grasp as
+ * Grasp2D.from_vector(...).as_4dof() in the world with the env's own calibration (rv_get_camera).  d_status [N]:
+ * RV_AP_*.  A row whose status is not RV_AP_OK carries the env's rv_policy_random draw for macro_index in
+ * d_actions4, and in d_image_grasps that draw's centre projected through the env's camera, [u, v, u, v, z].
+ * A grasp world only; invalid parameters: RV_ERR_VALUE. */
+int  rv_policy_antipodal(rv_world* w, const float* d_depth, const rv_antipodal_params* h_params, int32_t macro_index,
+                         float* d_image_grasps, float* d_actions4, int32_t* d_status);
+
 /* ---- Simulator.step x n (simulator.py:94-103): ControllableBody.update +
  *      BulletPhysics.step (bullet_physics.py:106-109), no phase machine. ---- */
 int  rv_step_sub(rv_world* w, int32_t n_substeps);

@@ -18,6 +18,9 @@ RV_NCOL = 10
 RV_MAXTILES = 24
 RV_MAXG = 4
 RV_MAXQ = 8
+RV_AP_MAX_RADIUS = 32
+RV_AP_MAX_EDGES = 4096
+RV_AP_OK, RV_AP_NO_EDGES, RV_AP_NO_PAIRS, RV_AP_ALL_REJECTED, RV_AP_TOO_MANY_EDGES = 1, 0, -1, -2, -3
 
 
 def RV_CHILD_LINK(f):
@@ -176,6 +179,18 @@ class rv_state_view(C.Structure):
         ('d_envs', C.c_void_p), ('env_stride_bytes', i64),
         ('off_body', i64), ('off_active', i64), ('off_joint_q', i64), ('off_joint_qd', i64),
         ('off_link_pos', i64), ('off_link_quat', i64), ('off_obs_pos', i64), ('off_table_z', i64),
+    ]
+
+
+class rv_antipodal_params(C.Structure):
+    _fields_ = [
+        ('friction_coef', f32), ('depth_grad_thresh', f32), ('depth_grad_gaussian_sigma', f32),
+        ('downsample_rate', i32), ('max_rejection_samples', i32), ('use_crop', i32), ('crop', i32 * 4),
+        ('min_dist_from_boundary', f32), ('min_grasp_dist', f32), ('angle_dist_weight', f32),
+        ('depth_samples_per_grasp', i32), ('min_depth_offset', f32), ('max_depth_offset', f32),
+        ('depth_sample_window_height', f32), ('depth_sample_window_width', f32),
+        ('gripper_width', f32), ('cone_cos', f32), ('gauss_radius', i32),
+        ('gauss_weights', f32 * (RV_AP_MAX_RADIUS + 1)),
     ]
 
 

@@ -195,6 +195,30 @@ HEURISTIC_PUSH_POLICY_CONFIG = {
     'HEURISTICS': {'MAX_ATTEMPS': 20000},
 }
 
+# AntipodalGrasp4DofPolicy (grasp_policy.py:17-75; configs/policies/antipodal_grasp_4dof_policy.yaml is not
+# distributed): the reference's SAMPLER keys + GRIPPER_WIDTH, values BUILD-CHOSEN for Grasp4DofEnv's default camera
+ANTIPODAL_GRASP_4DOF_POLICY_CONFIG = {
+    'SAMPLER': {
+        'FRICTION_COEF': 1.0,                 # finger pads and graspables are high-friction (FRICTION 0.5..1 + pads)
+        'DEPTH_GRAD_THRESH': 0.01,            # m per downsampled pixel: above the table's own slope (~0.006 at rate 2)
+        'DEPTH_GRAD_GAUSSIAN_SIGMA': 1.0,     # one pixel of smoothing keeps the 1-2 cm objects' edges sharp
+        'DOWNSAMPLE_RATE': 2,                 # a graspable spans ~20-30 pixels: rate 2 keeps ~10-15 across it
+        'MAX_REJECTION_SAMPLES': 4000,        # a few times the valid pairs of one object: the subset rarely runs out
+        'CROP': [160, 216, 256, 296],         # rows / cols holding SIM.GRASPABLE.POSE's x/y range at table height under
+                                              # the default camera (rows 187-224, cols 239-273 with the objects' size)
+                                              # plus a margin (tests/test_antipodal_host.py checks it)
+        'MIN_DIST_FROM_BOUNDARY': 6,          # > the depth window, and clear of the crop's edge
+        'MIN_GRASP_DIST': 2.5,                # (unused: one grasp per env)
+        'ANGLE_DIST_WEIGHT': 5.0,             # (unused: one grasp per env)
+        'DEPTH_SAMPLES_PER_GRASP': 1,         # one grasp per env
+        'MIN_DEPTH_OFFSET': 0.015,            # fingertips 1.5 cm below the top the camera sees ...
+        'MAX_DEPTH_OFFSET': 0.03,             # ... to 3 cm: the graspables are 2.8-4 cm tall
+        'DEPTH_SAMPLE_WINDOW_HEIGHT': 2,      # a 4 x 4 pixel window (~1 cm) for the centre depth
+        'DEPTH_SAMPLE_WINDOW_WIDTH': 2,
+    },
+    'GRIPPER_WIDTH': 0.038,                   # the modelled finger opening, 2 x (0.004 + stroke) - pads (scenes.make_arm)
+}
+
 
 def push_env_config(**overrides):
     cfg = AttrDict(copy.deepcopy(PUSH_ENV_CONFIG))

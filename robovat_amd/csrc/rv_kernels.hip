@@ -20,6 +20,7 @@
 #include "../../include/rovat.h"
 #include "rv_dev_env.h"
 #include "rv_dev_obs.h"
+#include "rv_dev_grasp_sampler.h"
 
 using namespace rv;
 
@@ -566,6 +567,8 @@ struct rv_world {
   // q_grid workgroups (what is resident at a time), d_q = [RV_Q_CTL_WORDS control words][RV_Q_NQ rings of q_ring slots];
   // q_launch numbers the queued launches, q_used: a queued launch ran since rv_get_stats last looked at its error word
   int q_grid; int* d_q; size_t q_cap; int q_launch; bool q_used;
+  // rv_policy_antipodal: the depth it renders itself, the per-env filter scratch (floats; grown on demand)
+  float* d_ap_depth; size_t ap_depth_cap; float* d_ap_scratch; size_t ap_scratch_cap;
 };
 
 static thread_local std::string g_err;
@@ -674,6 +677,14 @@ static int ensure_snaps(rv_world* w, size_t n) {
   w->n_snaps_cap = n;
   return RV_OK;
 }
+// a lazily grown device buffer of `n` floats (as ensure_snaps)
+static int ensure_floats(rv_world* w, float** buf, size_t* cap, size_t n) {
+  if (*cap >= n) return RV_OK;
+  if (*buf) { HIPCHK(hipStreamSynchronize(w->stream)); HIPCHK(hipFree(*buf)); *buf = nullptr; *cap = 0; }
+  HIPCHK(hipMalloc(buf, sizeof(float) * n));
+  *cap = n;
+  return RV_OK;
+}
 static int launch_point_cloud(rv_world* w, size_t n_snaps, float* d_out) {
   hipLaunchKernelGGL(k_point_cloud, dim3((unsigned)(n_snaps * RV_MAXB)), dim3(64), 0, w->stream,
                      w->d_snaps, (int)n_snaps, w->n, d_out, w->d_cfg, w->d_scene);
@@ -703,6 +714,7 @@ int rv_create(const rv_config* cfg, const rv_scene* scene, int device, rv_world*
   if (!w) return fail(RV_ERR_STATE, "rv_create: out of host memory");
   w->cfg = *cfg; w->device = device; w->n = cfg->n_envs; w->stream = nullptr; w->timed = false;
   w->d_snaps = nullptr; w->n_snaps_cap = 0;
+  w->d_ap_depth = nullptr; w->ap_depth_cap = 0; w->d_ap_scratch = nullptr; w->ap_scratch_cap = 0;
   {
     // one wave per env: with more envs than SIMDs the two-waves-per-SIMD build of the env kernel pays
     // (RV_ENV_OCC=1 / 2 in the environment forces a build: measurements)
@@ -744,6 +756,8 @@ int rv_destroy(rv_world* w) {
   (void)hipFree(w->d_cfg); (void)hipFree(w->d_scene);
   (void)hipFree(w->d_envs); (void)hipFree(w->d_stats); (void)hipFree(w->d_budget); if (w->d_q) (void)hipFree(w->d_q);
   if (w->d_snaps) (void)hipFree(w->d_snaps);
+  if (w->d_ap_depth) (void)hipFree(w->d_ap_depth);
+  if (w->d_ap_scratch) (void)hipFree(w->d_ap_scratch);
   (void)hipEventDestroy(w->ev0); (void)hipEventDestroy(w->ev1);
   delete w;
   return RV_OK;
@@ -1011,6 +1025,40 @@ int rv_render(rv_world* w, float* d_depth, uint8_t* d_segmask) {
   SIMPLE_LAUNCH(k_obs_snap, w->d_envs, w->n, w->d_snaps, w->d_scene);
   const size_t total = (size_t)w->n * (size_t)w->cfg.cam_height * (size_t)w->cfg.cam_width;
   hipLaunchKernelGGL(k_render, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, w->stream, w->d_snaps, w->n, d_depth, d_segmask, w->d_cfg, w->d_scene);
+  HIPCHK(hipGetLastError());
+  return RV_OK;
+}
+int rv_policy_antipodal(rv_world* w, const float* d_depth, const rv_antipodal_params* h_params, int32_t macro_index,
+                        float* d_image_grasps, float* d_actions4, int32_t* d_status) {
+  WCHK(w); NEED(h_params, "rv_policy_antipodal"); NEED(d_image_grasps, "rv_policy_antipodal"); NEED(d_status, "rv_policy_antipodal");
+  const rv_antipodal_params& p = *h_params;
+  if (w->cfg.env_type != RV_ENV_GRASP) return fail(RV_ERR_VALUE, "rv_policy_antipodal: a Grasp4DofEnv world only");
+  const int H = w->cfg.cam_height, W = w->cfg.cam_width;
+  if (p.downsample_rate < 1 || p.downsample_rate > 8) return fail(RV_ERR_VALUE, "rv_policy_antipodal: DOWNSAMPLE_RATE must be an integer in 1..8");
+  if (p.depth_samples_per_grasp != 1) return fail(RV_ERR_VALUE, "rv_policy_antipodal: DEPTH_SAMPLES_PER_GRASP must be 1 (one grasp per env)");
+  if (p.max_rejection_samples < 1) return fail(RV_ERR_VALUE, "rv_policy_antipodal: MAX_REJECTION_SAMPLES must be positive");
+  if (p.gauss_radius < 0 || p.gauss_radius > RV_AP_MAX_RADIUS) return fail(RV_ERR_VALUE, "rv_policy_antipodal: Gaussian radius int(4 sigma + 0.5) outside [0, RV_AP_MAX_RADIUS]");
+  const float wh = p.depth_sample_window_height, ww = p.depth_sample_window_width;
+  if (!(wh >= 1.0f && ww >= 1.0f && p.min_dist_from_boundary > (wh > ww ? wh : ww)))
+    return fail(RV_ERR_VALUE, "rv_policy_antipodal: need MIN_DIST_FROM_BOUNDARY > max(DEPTH_SAMPLE_WINDOW_HEIGHT, DEPTH_SAMPLE_WINDOW_WIDTH) >= 1");
+  if (!(p.cone_cos >= 0.0f && p.cone_cos <= 1.0f)) return fail(RV_ERR_VALUE, "rv_policy_antipodal: cone_cos = cos(arctan(FRICTION_COEF)) outside [0, 1]");
+  int r0 = 0, c0 = 0, r1 = H, c1 = W;
+  if (p.use_crop) { r0 = p.crop[0]; c0 = p.crop[1]; r1 = p.crop[2]; c1 = p.crop[3]; }
+  if (!(0 <= r0 && r0 < r1 && r1 <= H && 0 <= c0 && c0 < c1 && c1 <= W)) return fail(RV_ERR_VALUE, "rv_policy_antipodal: CROP must be 0 <= r0 < r1 <= H, 0 <= c0 < c1 <= W");
+  ApArgs a;
+  memset(&a, 0, sizeof(a));
+  a.p = p; a.H = H; a.W = W; a.r0 = r0; a.c0 = c0; a.Hc = r1 - r0; a.Wc = c1 - c0;
+  a.Hd = a.Hc / p.downsample_rate; a.Wd = a.Wc / p.downsample_rate;
+  if (a.Hd < 2 || a.Wd < 2) return fail(RV_ERR_VALUE, "rv_policy_antipodal: the downsampled crop must be at least 2 x 2");
+  a.macro_index = macro_index; a.grasps = d_image_grasps; a.actions4 = d_actions4; a.status = d_status;
+  if (!d_depth) {
+    int rc = ensure_floats(w, &w->d_ap_depth, &w->ap_depth_cap, (size_t)w->n * H * W); if (rc != RV_OK) return rc;
+    rc = rv_render(w, w->d_ap_depth, nullptr); if (rc != RV_OK) return rc;
+    d_depth = w->d_ap_depth;
+  }
+  int rc = ensure_floats(w, &w->d_ap_scratch, &w->ap_scratch_cap, (size_t)w->n * 2 * a.Hc * a.Wc); if (rc != RV_OK) return rc;
+  a.depth = d_depth; a.scratch = w->d_ap_scratch;
+  hipLaunchKernelGGL(k_policy_antipodal, dim3((unsigned)w->n), dim3(RV_AP_TPB), 0, w->stream, w->d_envs, w->n, w->d_cfg, a);
   HIPCHK(hipGetLastError());
   return RV_OK;
 }

@@ -42,6 +42,7 @@ class VecGrasp4DofEnv(object):
         else:
             raise ValueError('Unrecognized action type: %r' % (self.config.ACTION.TYPE,))
         self._macro_index = 0
+        self.antipodal_status = self.antipodal_image_grasps = None
 
     device = property(lambda s: s.world.device)
 
@@ -80,6 +81,18 @@ class VecGrasp4DofEnv(object):
     def sample_random_actions(self):
         """RandomPolicy = action_space.sample() on the device (uniform in ACTION.CUBOID x [0, 2 pi))."""
         return self.world.policy_random(self._macro_index).reshape(self.num_envs, 4)
+
+    def sample_antipodal_actions(self, depth=None, config=None):
+        """AntipodalGrasp4DofPolicy on the device (rv_policy_antipodal): one antipodal grasp per env from its depth
+        image (``depth`` [N, H, W]; None: rendered now), in the env's ACTION.TYPE -- [N, 4] world actions for
+        'CUBOID', [N, 5] image grasps for 'IMAGE'.  Rows without a grasp carry the env's RandomPolicy draw (see
+        ``antipodal_status``: 1 = grasp; 0 / -1 / -2 / -3 = no edge pixel / no valid pair / every candidate rejected /
+        too many edge pixels); the status and the image grasps stay on the env for recording."""
+        from robovat_amd import lib
+        cuboid = self.config.ACTION.TYPE == 'CUBOID'
+        g, a, st = self.world.policy_antipodal(lib.antipodal_params(config), self._macro_index, depth=depth, actions4=cuboid)
+        self.antipodal_status, self.antipodal_image_grasps = st, g
+        return a if cuboid else g
 
     def rollout(self, n_steps, auto_reset=True, record=True):
         out = self.world.rollout(n_steps, self._macro_index, auto_reset, record)
@@ -145,6 +158,17 @@ class Grasp4DofEnv(object):
 
     def get_observation(self):
         return self._obs_data
+
+    def sample_antipodal_actions(self, depth=None, config=None):
+        """AntipodalGrasp4DofPolicy's action for this env (the batch of one); ValueError when no grasp is found, as
+        the reference's sampler raises or returns none (image_grasp_sampler.py:359-360)."""
+        if depth is not None:
+            depth = np.asarray(depth, np.float32).reshape((1,) + np.shape(depth)[-2:])
+        a = self._vec.sample_antipodal_actions(depth, config)
+        status = int(self._vec.antipodal_status[0].item())
+        if status != 1:
+            raise ValueError('Failed to sample any valid grasp (antipodal status %d).' % status)
+        return a[0].cpu().numpy()
 
     def close(self):
         self._vec.close()

@@ -40,3 +40,18 @@ class HeuristicPushPolicy(Policy):
             return self.env.sample_heuristic_actions(self.config.HEURISTICS.MAX_ATTEMPS)
         return self._sampler.sample(np.asarray(observation['position']), np.asarray(observation['body_mask']),
                                     int(observation['num_episodes']), int(observation['num_steps']), num_samples=1)[0]
+
+
+class AntipodalGrasp4DofPolicy(Policy):
+    """grasp_policy.py:17-75: AntipodalDepthImageGraspSampler on the env's depth image.  Grasp envs sample on the
+    device (rv_policy_antipodal); the action is in the env's ACTION.TYPE."""
+
+    def __init__(self, env, config=None):
+        config = config or configs.AttrDict(configs.ANTIPODAL_GRASP_4DOF_POLICY_CONFIG)
+        super(AntipodalGrasp4DofPolicy, self).__init__(env, config)
+
+    def _action(self, observation):
+        if hasattr(self.env, 'sample_antipodal_actions'):
+            depth = None if observation is None else observation.get('depth')
+            return self.env.sample_antipodal_actions(depth, self.config)
+        raise NotImplementedError('AntipodalGrasp4DofPolicy needs a Grasp4DofEnv / VecGrasp4DofEnv')

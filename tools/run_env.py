@@ -4,6 +4,7 @@ matter for the hot path: run episodes of an env with a policy on the GPU.
 
     python tools/run_env.py --env PushEnv --policy HeuristicPushPolicy --num_episodes 20 --seed 0
     python tools/run_env.py --env VecPushEnv --num_envs 1024 --policy RandomPolicy --num_steps 50
+    python tools/run_env.py --env VecGrasp4DofEnv --num_envs 2048 --policy AntipodalGrasp4DofPolicy --num_steps 3
 """
 import argparse
 import os
@@ -32,6 +33,8 @@ def main():
     from robovat_amd import configs, envs, policies
     from robovat_amd.io.episode_generation import generate_episodes
     np.random.seed(args.seed)
+    if args.env in ('Grasp4DofEnv', 'VecGrasp4DofEnv'):
+        return run_grasp(args)
     cfg = configs.push_env_config(TASK_NAME=args.task, LAYOUT_ID=args.layout_id, MAX_STEPS=args.max_steps)
     if args.env == 'PushEnv':
         env = envs.PushEnv(config=cfg, seed=args.seed, worker_id=args.worker_id)
@@ -62,6 +65,42 @@ def main():
         st = env.stats()
         print('%d envs x %d steps: %.1f env steps/s, mean reward %.3f' % (
             args.num_envs, args.num_steps or 5, st['env_steps'] / (time.time() - t0), float(r.mean())))
+
+
+def run_grasp(args):
+    """Grasp4DofEnv (one env, the reference's API) or VecGrasp4DofEnv (N envs): num_steps x {action = policy(obs);
+    env.step(action)}; every episode is one grasp."""
+    import numpy as np
+    from robovat_amd import envs, policies
+    n_steps = args.num_steps or args.num_episodes
+    t0 = time.time()
+    if args.env == 'Grasp4DofEnv':
+        env = envs.Grasp4DofEnv(seed=args.seed, worker_id=args.worker_id)
+        policy = getattr(policies, args.policy)(env)
+        for i in range(n_steps):
+            obs = env.reset()
+            try:
+                action = policy.action(obs)
+            except ValueError as e:          # the reference's sampler found no grasp
+                print('episode %d: %s' % (i, e))
+                continue
+            _, reward, _, _ = env.step(action)
+            print('episode %d: action %s, reward %.1f, %.2f s' % (i, np.round(np.asarray(action), 4).tolist(), reward, time.time() - t0))
+        env.close()
+        return
+    env = envs.VecGrasp4DofEnv(args.num_envs, seed=args.seed)
+    policy = getattr(policies, args.policy)(env)
+    obs = env.reset()
+    for i in range(n_steps):
+        action = policy.action(obs)
+        obs, reward, done, _ = env.step(action)
+        line = 'step %d: success rate %.3f' % (i, float(reward.float().mean()))
+        if getattr(env, 'antipodal_status', None) is not None and args.policy == 'AntipodalGrasp4DofPolicy':
+            st = env.antipodal_status.cpu().numpy()
+            line += ', antipodal status %s' % {int(k): int((st == k).sum()) for k in np.unique(st)}
+        print(line + ', %.2f s' % (time.time() - t0))
+        obs = env.reset()
+    env.close()
 
 
 if __name__ == '__main__':
