@@ -525,6 +525,30 @@ int  rv_compute_ik(rv_world* w, const float* d_pose /* [N][7] */, float* d_q /* 
  *      (simulator.py:246-287, bullet_physics.py:1268-1304).
  *      d_out: uint8[N][2+RV_MAXB]: arm-table, arm-any-movable, arm-movable[b]. */
 int  rv_query_contacts(rv_world* w, uint8_t* d_out);
+/* ---- BulletPhysics.get_contact_points / pybullet.getContactPoints (bullet_physics.py:1262-1304), the records
+ *      behind Simulator.check_contact and Body.contacts (simulator.py:246-287), batched: one record per contact
+ *      point of every env, filtered by the query (-1 = any) and oriented so that body_a is body A.
+ *      Body codes: a body slot 0..RV_MAXB-1, RV_CP_TABLE, RV_CP_ARM.  Links: -1, or for the arm the
+ *      link frame of the collider (scenes.LINK_NAMES index); link_a / link_b only with the arm.
+ *      d_ids   int32[N][capacity][4]          bodyA, bodyB, linkA, linkB
+ *      d_data  float[N][capacity][RV_CP_NF]   positionOnA[3], positionOnB[3], contactNormalOnB[3], contactDistance,
+ *                                             normalForce, lateralFriction1, lateralFrictionDir1[3],
+ *                                             lateralFriction2, lateralFrictionDir2[3]  (forces: impulse / dt)
+ *      d_count int32[N]                       number of matching records (may exceed capacity: only the first
+ *                                             `capacity` are written, in manifold-slot / point order)
+ *      Gated so that for every pair "count > 0" equals the rv_query_contacts / manifold-count hit test; while the
+ *      arm-table flag is set a last record (arm, table, links -1, NaN positions and distance, normal +z, zero forces)
+ *      stands for it.  RV_ERR_VALUE: capacity outside [1, RV_CP_MAX], an unknown body code, a link for a body
+ *      that is not the arm.  Asynchronous on the world's stream. */
+#define RV_CP_NF    19
+#define RV_CP_TABLE RV_MAXB
+#define RV_CP_ARM   (RV_MAXB + 1)
+#define RV_CP_MAX   (RV_NMAN * 4 + 1)
+typedef struct rv_contact_query {
+  int32_t body_a, link_a, body_b, link_b;
+} rv_contact_query;
+int  rv_get_contact_points(rv_world* w, const rv_contact_query* q, int capacity,
+                           int32_t* d_ids, float* d_data, int32_t* d_count);
 /* ---- the camera calibration an env's observations are rendered with (Camera.intrinsics / translation / rotation,
  *      camera.py:150-168; the camera-calibration observations of camera_obs.py:241-320): rv_config's values plus the
  *      noise drawn at that env's last reset (cam_noise). */

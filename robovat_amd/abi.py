@@ -30,6 +30,11 @@ def RV_CHILD_LINK(f):
 RV_NBB = RV_MAXB * (RV_MAXB - 1) // 2
 RV_NMAN = 2 * RV_MAXB + RV_NBB
 RV_BODY_STRIDE = 13
+# rv_get_contact_points (include/rovat.h): record width, body codes of the table and the arm, records per env
+RV_CP_NF = 19
+RV_CP_TABLE = RV_MAXB
+RV_CP_ARM = RV_MAXB + 1
+RV_CP_MAX = RV_NMAN * 4 + 1
 RV_NCOUNTERS = 10
 
 RV_OK, RV_ERR_VALUE, RV_ERR_STATE, RV_ERR_HIP, RV_ERR_NOTIMPL = 0, 1, 2, 3, 4
@@ -192,6 +197,10 @@ class rv_antipodal_params(C.Structure):
         ('gripper_width', f32), ('cone_cos', f32), ('gauss_radius', i32),
         ('gauss_weights', f32 * (RV_AP_MAX_RADIUS + 1)),
     ]
+
+
+class rv_contact_query(C.Structure):
+    _fields_ = [('body_a', i32), ('link_a', i32), ('body_b', i32), ('link_b', i32)]
 
 
 def assign(arr, values):

@@ -4,6 +4,7 @@
 // Kernel inventory:
 //   k_env<MODE>     one wave64 per env, the whole reset / macro step / n
 //                   substeps / settle loop out of LDS (rv_dev_env.h)
+//   k_contact_points one wave64 per env: the PyBullet contact records (rv_dev_contacts.h)
 //   k_*             small one-thread-per-env accessors behind the getters,
 //                   setters, observation, reward and policy entry points
 #include <hip/hip_runtime.h>
@@ -21,6 +22,7 @@
 #include "rv_dev_env.h"
 #include "rv_dev_obs.h"
 #include "rv_dev_grasp_sampler.h"
+#include "rv_dev_contacts.h"
 
 using namespace rv;
 
@@ -997,6 +999,21 @@ int rv_compute_ik(rv_world* w, const float* d_pose, float* d_q) {
   SIMPLE_LAUNCH(k_compute_ik, w->d_envs, w->n, d_pose, d_q, w->d_cfg, w->d_scene); return RV_OK;
 }
 int rv_query_contacts(rv_world* w, uint8_t* d) { WCHK(w); NEED(d, "rv_query_contacts"); SIMPLE_LAUNCH(k_query_contacts, w->d_envs, w->n, d); return RV_OK; }
+int rv_get_contact_points(rv_world* w, const rv_contact_query* q, int capacity, int32_t* d_ids, float* d_data, int32_t* d_count) {
+  WCHK(w); NEED(q, "rv_get_contact_points"); NEED(d_ids, "rv_get_contact_points"); NEED(d_data, "rv_get_contact_points"); NEED(d_count, "rv_get_contact_points");
+  if (capacity < 1 || capacity > RV_CP_MAX) return fail(RV_ERR_VALUE, "rv_get_contact_points: capacity outside [1, RV_CP_MAX]");
+  const int body[2] = {q->body_a, q->body_b}, link[2] = {q->link_a, q->link_b};
+  for (int s = 0; s < 2; ++s) {
+    if (body[s] < -1 || body[s] > RV_CP_ARM) return fail(RV_ERR_VALUE, "rv_get_contact_points: unknown body code " + std::to_string(body[s]));
+    if (link[s] < -1 || link[s] >= RV_NFRAME) return fail(RV_ERR_VALUE, "rv_get_contact_points: link outside [-1, RV_NFRAME)");
+    if (link[s] >= 0 && body[s] != RV_CP_ARM) return fail(RV_ERR_VALUE, "rv_get_contact_points: a link index is only meaningful for the arm (RV_CP_ARM)");
+  }
+  CpArgs a; a.q = *q; a.capacity = capacity; a.ids = d_ids; a.data = d_data; a.count = d_count;
+  hipLaunchKernelGGL(k_contact_points, dim3((unsigned)((w->n + RV_CP_WAVES - 1) / RV_CP_WAVES)), dim3(64 * RV_CP_WAVES), 0, w->stream,
+                     w->d_envs, w->n, w->d_cfg, w->d_scene, a);
+  HIPCHK(hipGetLastError());
+  return RV_OK;
+}
 int rv_get_manifold_counts(rv_world* w, int32_t* d) { WCHK(w); NEED(d, "rv_get_manifold_counts"); SIMPLE_LAUNCH(k_manifold_counts, w->d_envs, w->n, d); return RV_OK; }
 int rv_observe(rv_world* w, const rv_obs_buffers* obs) {
   WCHK(w); NEED(obs, "rv_observe");

@@ -94,6 +94,15 @@ class VecGrasp4DofEnv(object):
         self.antipodal_status, self.antipodal_image_grasps = st, g
         return a if cuboid else g
 
+    def contact_points(self, body_a=-1, link_a=-1, body_b=-1, link_b=-1, capacity=abi.RV_CP_MAX):
+        """PyBullet contact records of every env on the device (``lib.World.contact_points``): ids [N, P, 4],
+        data [N, P, RV_CP_NF], count [N]; bodies are slots, ``abi.RV_CP_TABLE`` or ``abi.RV_CP_ARM``."""
+        return self.world.contact_points(body_a, link_a, body_b, link_b, capacity)
+
+    def contact_forces(self, body_a=-1, link_a=-1, body_b=-1, link_b=-1):
+        """Net contact force on body A, [N, 3] on the device (``lib.World.contact_forces``)."""
+        return self.world.contact_forces(body_a, link_a, body_b, link_b)
+
     def rollout(self, n_steps, auto_reset=True, record=True):
         out = self.world.rollout(n_steps, self._macro_index, auto_reset, record)
         self._macro_index += int(n_steps)

@@ -104,6 +104,15 @@ class VecPushEnv(object):
         a = self.world.policy_heuristic(max_attempts)
         return a.reshape((self.num_envs,) + self.action_shape)
 
+    def contact_points(self, body_a=-1, link_a=-1, body_b=-1, link_b=-1, capacity=abi.RV_CP_MAX):
+        """PyBullet contact records of every env on the device (``lib.World.contact_points``): ids [N, P, 4],
+        data [N, P, RV_CP_NF], count [N]; bodies are slots, ``abi.RV_CP_TABLE`` or ``abi.RV_CP_ARM``."""
+        return self.world.contact_points(body_a, link_a, body_b, link_b, capacity)
+
+    def contact_forces(self, body_a=-1, link_a=-1, body_b=-1, link_b=-1):
+        """Net contact force on body A, [N, 3] on the device (``lib.World.contact_forces``)."""
+        return self.world.contact_forces(body_a, link_a, body_b, link_b)
+
     def rollout(self, n_steps, auto_reset=True, record=True):
         before = self.world.env_counters().cpu().numpy()[:, [2, 4]] if (auto_reset and self._physics is not None) else None
         out = self.world.rollout(n_steps, self._macro_index, auto_reset, record)

@@ -32,7 +32,7 @@ SYMBOLS = [
     'rv_reset_targets', 'rv_get_state_ptrs', 'rv_source_hash', 'rv_set_motor_targets', 'rv_grip',
     'rv_rollout_record', 'rv_render', 'rv_set_gravity', 'rv_rollout_record_full', 'rv_step_begin', 'rv_step_poll', 'rv_set_constraint', 'rv_render_rgb', 'rv_set_friction', 'rv_set_auto_reset',
     'rv_set_constraint_ex', 'rv_set_link_path', 'rv_get_robot_ready', 'rv_get_camera', 'rv_set_max_joint_velocities',
-    'rv_policy_antipodal',
+    'rv_policy_antipodal', 'rv_get_contact_points',
 ]
 
 _EXC = {abi.RV_ERR_VALUE: ValueError, abi.RV_ERR_STATE: RuntimeError,
@@ -166,6 +166,7 @@ def load():
     lib.rv_set_max_joint_velocities.argtypes = [vp, vp]
     lib.rv_get_camera.argtypes = [vp, vp]
     lib.rv_policy_antipodal.argtypes = [vp, vp, C.POINTER(abi.rv_antipodal_params), i32, vp, vp, vp]
+    lib.rv_get_contact_points.argtypes = [vp, C.POINTER(abi.rv_contact_query), i32, vp, vp, vp]
     for name in ('rv_set_actions', 'rv_get_body_state', 'rv_set_body_state',
                  'rv_get_body_params', 'rv_set_body_params', 'rv_get_joint_state',
                  'rv_set_joint_state', 'rv_get_link_poses', 'rv_get_env_counters',
@@ -556,6 +557,29 @@ class World(object):
 
     def manifold_counts(self):
         return self._get('rv_get_manifold_counts', (self.n, abi.RV_NMAN), self.torch.int32)
+
+    def contact_points(self, body_a=-1, link_a=-1, body_b=-1, link_b=-1, capacity=abi.RV_CP_MAX):
+        """rv_get_contact_points: PyBullet's contact records (getContactPoints) of every env, filtered by the query
+        (-1 = any; bodies are slots 0..RV_MAXB-1, RV_CP_TABLE, RV_CP_ARM; links only for the arm) and oriented so
+        that body_a is body A.  Returns device tensors, with no host sync: ids int32 [N, capacity, 4] (bodyA, bodyB,
+        linkA, linkB), data float32 [N, capacity, RV_CP_NF] (positionOnA, positionOnB, contactNormalOnB,
+        contactDistance, normalForce, lateralFriction1, lateralFrictionDir1, lateralFriction2, lateralFrictionDir2)
+        and count int32 [N] -- the number of matches; only the first min(count, capacity) rows are written."""
+        q = abi.rv_contact_query(int(body_a), int(link_a), int(body_b), int(link_b))
+        cap = int(capacity)
+        ids = self._new((self.n, max(cap, 1), 4), self.torch.int32)
+        data = self._new((self.n, max(cap, 1), abi.RV_CP_NF), self.torch.float32)
+        count = self._new((self.n,), self.torch.int32)
+        check(self.lib.rv_get_contact_points(self.h, C.byref(q), cap, self._ptr(ids), self._ptr(data), self._ptr(count)))
+        return ids, data, count
+
+    def contact_forces(self, body_a=-1, link_a=-1, body_b=-1, link_b=-1):
+        """The net contact force on body A, [N, 3] float32 on the device: fn n + f1 d1 + f2 d2 summed over the records
+        of contact_points(...) (n points from B to A)."""
+        ids, data, count = self.contact_points(body_a, link_a, body_b, link_b)
+        valid = self.torch.arange(data.shape[1], device=self.device)[None, :] < count[:, None]
+        f = (data[..., 10:11] * data[..., 6:9] + data[..., 11:12] * data[..., 12:15] + data[..., 15:16] * data[..., 16:19])
+        return self.torch.where(valid[..., None], f, self.torch.zeros_like(f)).sum(dim=1)
 
     def observe(self, point_cloud=False, pose_modes=False):
         out, b = self._obs_buffers((self.n,), point_cloud, pose_modes)

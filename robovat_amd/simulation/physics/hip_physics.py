@@ -438,36 +438,52 @@ class HipPhysics(Physics):
         js = self._np(self._world.joint_state())[0, :, 0]
         return list(q) + list(js[7:])
 
-    # ---- contacts (bullet_physics.py:1268-1304): the LENGTH of the list is what callers use
+    # ---- contacts (bullet_physics.py:1262-1304): pybullet.getContactPoints of env 0, from rv_get_contact_points
+    def _contact_side(self, uid):
+        """(body code, link) of an entity for rv_contact_query, or None for an entity that has no contacts (a visual-only
+        static body, a link other than -1 of a body)."""
+        if isinstance(uid, (int, np.integer)):
+            body, link = int(uid), -1
+        elif isinstance(uid, (tuple, list)):
+            body, link = int(uid[0]), int(uid[1])
+        else:
+            raise ValueError('not a body uid or (body uid, link index): %r' % (uid,))
+        if body == ARM_UID:
+            return abi.RV_CP_ARM, link
+        if link != -1:
+            return None      # (a body or the table has only its base, link -1: PyBullet finds no contact of another link)
+        if body == TABLE_UID:
+            return abi.RV_CP_TABLE, -1
+        if 0 <= body < abi.RV_MAXB:
+            return body, -1
+        return None
+
+    def _contact_records(self, a_uid, b_uid):
+        a = self._contact_side(a_uid)
+        b = (-1, -1) if b_uid is None else self._contact_side(b_uid)
+        if a is None or b is None:
+            return np.zeros((0, 4), np.int32), np.zeros((0, abi.RV_CP_NF), np.float32)
+        ids, data, count = self._world.contact_points(a[0], a[1], b[0], b[1])
+        k = min(int(count[0]), abi.RV_CP_MAX)
+        return self._np(ids[0, :k]), self._np(data[0, :k])
+
     def get_contact_points(self, a_uid, b_uid=None):
-        def body(uid):
-            if isinstance(uid, (int, np.integer)):
-                return int(uid)
-            if isinstance(uid, (tuple, list)):
-                return int(uid[0])
-            raise ValueError
-        a = body(a_uid)
-        b = None if b_uid is None else body(b_uid)
-        flags = self._np(self._world.query_contacts())[0]
-        counts = self._np(self._world.manifold_counts())[0]
-        if b is not None and a != ARM_UID and b == ARM_UID:
-            a, b = b, a
-        hit = False
-        if a == ARM_UID:
-            if b is None:
-                hit = bool(flags[0] or flags[1])
-            elif b == TABLE_UID:
-                hit = bool(flags[0])
-            elif 0 <= b < abi.RV_MAXB:
-                hit = bool(flags[2 + b])
-        elif 0 <= a < abi.RV_MAXB:
-            if b is None or b == TABLE_UID:
-                hit = counts[a] > 0
-            if (b is None or (0 <= b < abi.RV_MAXB)) and not hit:
-                for k, (x, y) in enumerate([(0, 1), (0, 2), (0, 3), (1, 2), (1, 3), (2, 3)]):
-                    if a in (x, y) and (b is None or b in (x, y)) and counts[abi.RV_MAXB + k] > 0:
-                        hit = True
-        return [0.0] if hit else []
+        """One entry per contact point, ``cp[-1]`` (lateralFrictionDir2) of PyBullet's record, as the reference returns
+        them; the LENGTH of the list is what callers use.  A link of the arm, ``(ARM_UID, link)``, narrows the query to
+        that link (the table flag of the arm matches every link: it does not say which link touched)."""
+        _, data = self._contact_records(a_uid, b_uid)
+        return [tuple(float(x) for x in r[16:19]) for r in data]
+
+    def get_contact_point_records(self, a_uid, b_uid=None):
+        """PyBullet's 14-field records (contactFlag 0, bodyUniqueIdA, bodyUniqueIdB, linkIndexA, linkIndexB, positionOnA,
+        positionOnB, contactNormalOnB, contactDistance, normalForce, lateralFriction1, lateralFrictionDir1,
+        lateralFriction2, lateralFrictionDir2) with this backend's uids, oriented so that ``a_uid`` is body A."""
+        ids, data = self._contact_records(a_uid, b_uid)
+        uid = {abi.RV_CP_TABLE: TABLE_UID, abi.RV_CP_ARM: ARM_UID}
+        v3 = lambda r, k: tuple(float(x) for x in r[k:k + 3])
+        return [(0, uid.get(int(i[0]), int(i[0])), uid.get(int(i[1]), int(i[1])), int(i[2]), int(i[3]),
+                 v3(r, 0), v3(r, 3), v3(r, 6), float(r[9]), float(r[10]), float(r[11]), v3(r, 12), float(r[15]), v3(r, 16))
+                for i, r in zip(ids, data)]
 
     # ---- not on the PushEnv / grasp paths (SURVEY.md §8b: "implement last / stub")
     # ---- user constraints (bullet_physics.py:748-957: createConstraint / changeConstraint / removeConstraint)
