@@ -42,6 +42,10 @@ struct EpaWork {
   int ea[RV_EPA_MAX_EDGES], eb[RV_EPA_MAX_EDGES];
 };
 
+// What one convex query found, staged until the queries of its round are done (rv_dev_env.h: collide_query / collide_apply):
+// hit, normal, distance, the two witness points, the simplex-cache record the query left (packed: gc_pack)
+struct QStage { int hit; float n[3], d, pa[3], pb[3]; unsigned gc; };
+
 // persistent manifold (one per pair slot), 63 words
 struct DevMan {
   int n;

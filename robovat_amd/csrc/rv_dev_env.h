@@ -29,8 +29,19 @@
 namespace rv {
 
 #if RV_ON_DEVICE
+// The env program runs with ONE wave per workgroup (k_env: __launch_bounds__(RV_ENV_THREADS)), and the LDS operations
+// of one wave complete in the order they were issued.  What a lane phase stored is therefore seen by the loads of the
+// next phase without waiting for the stores to finish: a phase boundary only has to stop the COMPILER from moving LDS
+// accesses across it (a wavefront-scope fence + wave_barrier; no instruction).  __syncthreads() would add the
+// workgroup-scope fence, an s_waitcnt lgkmcnt(0) that exposes one LDS store latency per boundary.  It stays where
+// global memory is ordered or a workgroup holds several waves (rv_env_kernel.h, the other kernels).
+// (FLAT accesses that land in LDS are NOT in that order.  The only ones of the env program are the hull-vertex reads of
+// the out-of-line epa(), behind GJK iterations that have read the same arrays with DS loads and used the values.)
+#define RV_ENV_THREADS 64
+static_assert(RV_ENV_THREADS == 64, "RV_WAVE_SYNC is a phase boundary only while a workgroup of k_env is one wave64");
+#define RV_WAVE_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); } while (0)
 #define RV_LANES_BEGIN { const int lane = (int)threadIdx.x;
-#define RV_LANES_END } __syncthreads();
+#define RV_LANES_END } RV_WAVE_SYNC();
 // a value every lane holds alike (read from the env's LDS block), moved to the scalar unit so that the control flow
 // that hangs on it is compiled as uniform
 #define RV_UNI(x) __builtin_amdgcn_readfirstlane((int)(x))
@@ -243,10 +254,14 @@ struct Scratch {
   int any_on;
   int pairs[4];
   // narrow-phase work list (per substep): refreshed distances / break flags per cached point,
-  // (body, collider box) proximity flags, the owners that have convex queries to run
+  // (body, collider box) proximity flags, the owners that have convex queries to run.  The queries are dealt to the
+  // 16-lane groups by convex PAIR: the items (owner, pair) form one flat list in owner order, then pair order;
+  // olist[k] = owner + 256 x the index of its first item, n_items = the length of the flat list
+  // (ow_run: host emulation only, the owner's pair count before its far collider boxes are dropped)
   float rf_dist[RV_NMAN * 4]; int rf_rm[RV_NMAN * 4];
   int cn[RV_MAXB][RV_NCOL];
-  int ow_run[RV_NMAN + RV_NCOL], olist[RV_NMAN + RV_NCOL], n_olist;
+  int ow_run[RV_NMAN + RV_NCOL], olist[RV_NMAN + RV_NCOL], n_olist, n_items;
+  QStage qst[4];                         // what the queries of the running round found, one slot per group
   int wvneed[RV_MAXB];                   // body has hulls in a convex query of this substep
 #if !RV_ON_DEVICE
   int rowmap[120], n_rows;   // host emulation of the impulse-space solver: rows in visiting order
@@ -589,12 +604,12 @@ RV_DEV void arm_ik_wave(Shared& S, const Consts& K) {
     for (int i = 1; i < RV_NLIMB; ++i) if (j == i) { axj = F.axis[i]; pj = F.pos[i]; }
     const v3 cr = cross(axj, sub(F.pos[7], pj));
     const float Jc[6] = {cr.x, cr.y, cr.z, axj.x, axj.y, axj.z};
-    __syncthreads();                       // (the previous iteration's readers of ik_J are done)
+    RV_WAVE_SYNC();                       // (the previous iteration's readers of ik_J are done)
     if (lane < RV_NLIMB) {
 #pragma unroll
       for (int r = 0; r < 6; ++r) S.s.ik_J[r][lane] = Jc[r];
     }
-    __syncthreads();
+    RV_WAVE_SYNC();
     float Ars;
     {
       float acc = 0.0f;
@@ -638,10 +653,10 @@ RV_DEV void arm_ik_wave(Shared& S, const Consts& K) {
     const float sc = mx > c->ik_max_step ? c->ik_max_step / mx : 1.0f;
     q = fclampr(q + dq * sc, qlo, qhi);
   }
-  __syncthreads();
+  RV_WAVE_SYNC();
   if (lane < RV_NLIMB) S.s.ik_q[lane] = q;
   if (lane == 0) S.s.ik_conv = conv;
-  __syncthreads();
+  RV_WAVE_SYNC();
 }
 #endif
 // ControllableBody.update for the env: every lane calls it
@@ -808,27 +823,63 @@ RV_DEV void manifold_add_world(const Shared& S, const Consts& K, int kind, int a
 #define RV_MAN_TAU 0.1f
 #define RV_FEATURE_PERIOD 4
 
-// narrow phase of one convex pair; m == nullptr: distance only
-RV_DEV int collide_pair(const Shared& S, const Consts& K, int kind, int a, int b, int col,
-                        const float* A, int nA, const float* B, int nB, v3 guess, DevMan* m, float* out_dist, const float brk, const int pair) {
+// Narrow phase of one convex pair in two parts, so that the queries of different pairs of ONE
+// manifold can run side by side (sim_substep_heavy):
+//   collide_query   GJK / EPA and the acceptance tests.  Touches no manifold: the result goes to a QStage, the simplex
+//                   cache it read is a private copy and the record it would have left is staged with the result;
+//   collide_apply   the staged result enters the manifold: cache record, closest point, the `age` test, feature stage.
+//                   The applies of one manifold run in pair order (man_add and the age test see the pair before).
+struct PairItem {
+  int role, ckind, a, b, col, mi, pair;   // pair: which pair of hulls of the manifold (the key of its simplex cache)
+  const float* A; const float* B; int nA, nB;
+  v3 guess; float brk;
+};
+// the simplex-cache record of a query as one word: n + 4 bits per vertex index (n = 0: the query left the cache empty)
+static_assert(RV_MAXV <= 16, "GjkCache indices are packed in 4 bits");
+RV_DEV unsigned gc_pack(const GjkCache& g) {
+  unsigned w = (unsigned)g.n;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) if (i < g.n) w |= ((unsigned)g.ia[i] & 15u) << (2 + 4 * i) | ((unsigned)g.ib[i] & 15u) << (14 + 4 * i);
+  return w;
+}
+// gc: the cache the query starts from (a private copy; nullptr: none) -- on return what the query left in it
+RV_DEV void collide_query(const Consts& K, const PairItem& p, GjkCache* gc, QStage& st) {
   float mg = K.cfg->margin;
   v3 n, pa, pb; float dist;
   RV_PROFG(0)
-  const int hit_ = gjk_epa(A, nA, B, nB, guess, brk + 2.0f * mg, &n, &dist, &pa, &pb, nullptr, m ? &m->gc : nullptr, pair);
+  const int hit_ = gjk_epa(p.A, p.nA, p.B, p.nB, p.guess, p.brk + 2.0f * mg, &n, &dist, &pa, &pb, nullptr, gc, p.pair);
   RV_PROFG(1)
-  if (!hit_) return 0;
+  st.hit = 0; st.gc = gc ? gc_pack(*gc) : 0u;
+  if (!hit_) return;
   float d = dist - 2.0f * mg;
-  if (d > brk) return 0;
-  if (!(dot(n, n) > 0.5f)) return 0;   // safety net: never accept a non-unit normal
-  *out_dist = d;
-  if (!m) return 1;
+  if (d > p.brk) return;
+  if (!(dot(n, n) > 0.5f)) return;   // safety net: never accept a non-unit normal
+  st.hit = 1; st.d = d;
+  st3(st.n, n); st3(st.pa, pa); st3(st.pb, pb);
+}
+RV_DEV void collide_apply(const Shared& S, const Consts& K, const PairItem& p, DevMan* m, const QStage& st) {
+  const int kind = p.ckind, a = p.a, b = p.b, col = p.col; const float brk = p.brk;
+  const float* A = p.A; const float* B = p.B; const int nA = p.nA, nB = p.nB;
+  float mg = K.cfg->margin;
+  {
+    // the simplex cache as the query would have left it: emptied on entry, written on its normal exit
+    const unsigned w = st.gc; const int gn = (int)(w & 3u);
+    m->gc.n = gn;
+    if (gn > 0) {
+      m->gc.pair = p.pair;
+#pragma unroll
+      for (int i = 0; i < 3; ++i) if (i < gn) { m->gc.ia[i] = (int)((w >> (2 + 4 * i)) & 15u); m->gc.ib[i] = (int)((w >> (14 + 4 * i)) & 15u); }
+    }
+  }
+  if (!st.hit) return;
+  const v3 n = ld3(st.n), pa = ld3(st.pa), pb = ld3(st.pb); const float d = st.d;
   manifold_add_world(S, K, kind, a, b, col, *m, madd(pa, n, -mg), madd(pb, n, mg), n, d, brk);
   RV_PROFG(2)
   // feature stage: only while the manifold is incomplete, or every
   // RV_FEATURE_PERIOD-th full pass (cached points are refreshed every substep)
   {
     int age = m->age;
-    if (m->n >= 4 && age < RV_FEATURE_PERIOD - 1) { m->age = age + 1; return 1; }
+    if (m->n >= 4 && age < RV_FEATURE_PERIOD - 1) { m->age = age + 1; return; }
     m->age = 0;
   }
   // candidate vertices are picked along four tangent directions rotated off the plane axes (a box
@@ -876,7 +927,6 @@ RV_DEV int collide_pair(const Shared& S, const Consts& K, int kind, int a, int b
     }
   }
   RV_PROFG(3)
-  return 1;
 }
 
 RV_DEV float sphere_aabb_dist2(v3 p, const float* lo, const float* hi) {
@@ -964,6 +1014,45 @@ RV_DEV void owner_decode(const Shared& S, const Consts& K, int owner, int arm_on
       if (!(minz - e.table_z - c->margin >= c->contact_query_dist) &&
           sphere_box_dist2(ld3(S.s.colc[col]), tc, th) < r * r) { o.role = 3; o.n_outer = 1; o.n_inner = 1; }
     }
+  }
+}
+
+// Item k of an owner that runs queries (sim_substep_heavy): its k-th convex pair in pair order -- for an arm-body owner
+// the pairs of the collider boxes near the body only (S.s.cn) -- with everything the query and the apply part need of it.
+RV_DEV void item_decode(const Shared& S, const Consts& K, const int owner, const int k, PairItem& p) {
+  const rv_config* c = K.cfg; const DevEnv& e = S.e;
+  p.col = -1; p.b = -1; p.mi = owner; p.guess = mk(0.0f, 0.0f, 1.0f);
+  if (owner < RV_MAXB) {
+    const int a = owner, ii = k, below = body_below_table(e, c, a);
+    p.role = 0; p.ckind = 0; p.a = a;
+    p.A = &S.s.u.r.wv[a][ii][0][0]; p.nA = S.n_verts[a][ii]; p.B = below ? &S.s.groundv[0][0] : &S.s.tablev[0][0]; p.nB = 8;
+    if (!below) p.guess = mk(0.0f, 0.0f, e.body[a][2] - (e.table_z - 0.5f * c->table_thickness));
+    p.pair = ii + (below ? 64 : 0);
+    p.brk = brk_of(e, K.arm, c, 0, a, -1, -1);
+  } else if (owner < RV_MAXB + RV_NBB) {
+    const int a = bb_a(owner - RV_MAXB), b = bb_b(owner - RV_MAXB), n_inner = S.n_hulls[b];
+    const int io = k / n_inner, ii = k - io * n_inner;
+    p.role = 1; p.ckind = 1; p.a = a; p.b = b;
+    p.A = &S.s.u.r.wv[a][io][0][0]; p.nA = S.n_verts[a][io]; p.B = &S.s.u.r.wv[b][ii][0][0]; p.nB = S.n_verts[b][ii];
+    p.guess = sub(ld3(e.body[a]), ld3(e.body[b]));
+    p.pair = io * 8 + ii;
+    p.brk = brk_of(e, K.arm, c, 1, a, b, -1);
+  } else if (owner < RV_NMAN) {
+    const int a = owner - RV_MAXB - RV_NBB, n_inner = S.n_hulls[a];
+    int j = k / n_inner; const int ii = k - j * n_inner;
+    int col = 0;
+    for (int x = 0; x < RV_NCOL; ++x) if (S.s.cn[a][x]) { if (j == 0) col = x; --j; }     // the j-th near box
+    p.role = 2; p.ckind = 2; p.a = a; p.col = col;
+    p.A = &S.s.u.r.wv[a][ii][0][0]; p.nA = S.n_verts[a][ii]; p.B = &S.s.colv[col][0][0]; p.nB = 8;
+    p.guess = sub(ld3(e.body[a]), ld3(S.s.colc[col]));
+    p.pair = col * 8 + ii;
+    p.brk = brk_of(e, K.arm, c, 2, a, -1, col);
+  } else {
+    const int col = owner - RV_NMAN;
+    p.role = 3; p.ckind = 0; p.a = 0; p.col = col; p.mi = 0;
+    p.A = &S.s.colv[col][0][0]; p.nA = 8; p.B = &S.s.tablev[0][0]; p.nB = 8;
+    p.pair = 0;
+    p.brk = brk_col(K.arm, c, col);
   }
 }
 
@@ -1691,7 +1780,7 @@ RV_DEV void solve_island2(Shared& S, const Consts& K, const int X, const int Y, 
     o[0] = PX.l.x; o[1] = PX.l.y; o[2] = PX.l.z; o[3] = PX.a.x; o[4] = PX.a.y; o[5] = PX.a.z;
     o[6] = PY.l.x; o[7] = PY.l.y; o[8] = PY.l.z; o[9] = PY.a.x; o[10] = PY.a.y; o[11] = PY.a.z;
   }
-  __syncthreads();
+  RV_WAVE_SYNC();
   float A[60];
 #pragma unroll
   for (int s = 0; s < 60; ++s) {
@@ -1704,7 +1793,7 @@ RV_DEV void solve_island2(Shared& S, const Consts& K, const int X, const int Y, 
     }
     A[s] = a_;
   }
-  __syncthreads();          // (cb is written again by the epilogue)
+  RV_WAVE_SYNC();          // (cb is written again by the epilogue)
   // warm start: the impulses kept from the last substep act first, in visiting order (X and Y slot
   // by slot, then the pair manifold)
 #pragma unroll
@@ -1784,7 +1873,7 @@ RV_DEV void solve_island2(Shared& S, const Consts& K, const int X, const int Y, 
     o[0] = PX.l.x * lam; o[1] = PX.l.y * lam; o[2] = PX.l.z * lam; o[3] = PX.a.x * lam; o[4] = PX.a.y * lam; o[5] = PX.a.z * lam;
     o[6] = PY.l.x * lam; o[7] = PY.l.y * lam; o[8] = PY.l.z * lam; o[9] = PY.a.x * lam; o[10] = PY.a.y * lam; o[11] = PY.a.z * lam;
   }
-  __syncthreads();
+  RV_WAVE_SYNC();
   if (lane < 12) {
     const int isy = lane >= 6, cc = lane - 6 * isy, bd = isy ? Y : X;
     const float* src = cb + 6 * isy + cc;
@@ -1802,7 +1891,7 @@ RV_DEV void solve_island2(Shared& S, const Consts& K, const int X, const int Y, 
     for (int s = 0; s < 12; ++s) acc = acc + t[s];
     e.body[bd][7 + cc] = acc;
   }
-  __syncthreads();
+  RV_WAVE_SYNC();
 }
 // ALL islands that are ONE body -- on the table (or the ground), touched by the arm or not; no point with another
 // awake body, no finger / limb / constraint rows -- solved TOGETHER: 16 lanes per body, lane 16 b + 3 p + k holds row k of
@@ -1946,7 +2035,7 @@ RV_DEV void solve_singles(Shared& S, const Consts& K, const int smask, const int
     o[0] = PT.l.x; o[1] = PT.l.y; o[2] = PT.l.z; o[3] = PT.a.x; o[4] = PT.a.y; o[5] = PT.a.z;
     if (arms) { o[6] = PA.l.x; o[7] = PA.l.y; o[8] = PA.l.z; o[9] = PA.a.x; o[10] = PA.a.y; o[11] = PA.a.z; }
   }
-  __syncthreads();
+  RV_WAVE_SYNC();
   // (column s of the matrix, as this lane's rows see it; then in target form: C = -(A invk), C_ss = 1 - A_ss invk_s)
   float CTT[12], CTA[12], CAT[12], CAA[12];
   float lsT[12], lsA[12];
@@ -1968,7 +2057,7 @@ RV_DEV void solve_singles(Shared& S, const Consts& K, const int smask, const int
       CAA[s] = dotj(JA, mk(q[6], q[7], q[8]), mk(q[9], q[10], q[11]));
     }
   }
-  __syncthreads();          // (cb is written again by the epilogue)
+  RV_WAVE_SYNC();          // (cb is written again by the epilogue)
   // warm start, in visiting order: the table rows, then the arm rows
 #pragma unroll
   for (int s = 0; s < 12; ++s) if (s / 3 < nt) { gT = gT + CTT[s] * lsT[s]; if (arms) gA = gA + CAT[s] * lsT[s]; }
@@ -2009,7 +2098,7 @@ RV_DEV void solve_singles(Shared& S, const Consts& K, const int smask, const int
     o[0] = PT.l.x * lamT; o[1] = PT.l.y * lamT; o[2] = PT.l.z * lamT; o[3] = PT.a.x * lamT; o[4] = PT.a.y * lamT; o[5] = PT.a.z * lamT;
     if (arms) { o[6] = PA.l.x * lamA; o[7] = PA.l.y * lamA; o[8] = PA.l.z * lamA; o[9] = PA.a.x * lamA; o[10] = PA.a.y * lamA; o[11] = PA.a.z * lamA; }
   }
-  __syncthreads();
+  RV_WAVE_SYNC();
   if (r < 6 && (nt + na) > 0) {
     float acc = e.body[b][7 + r];
     float t[12];
@@ -2025,7 +2114,7 @@ RV_DEV void solve_singles(Shared& S, const Consts& K, const int smask, const int
     } else acc = acc + 0.0f;        // (the twelve -- empty -- arm rows of the row list: +0.0 each)
     e.body[b][7 + r] = acc;
   }
-  __syncthreads();
+  RV_WAVE_SYNC();
 }
 // The force-limited gripper in impulse space (rv_config.finger_dynamics; at most one awake body X, or
 // none: X < 0).  Layout: lanes 0..23 the rows of X (table points 0..3, arm points 0..3, x 3 rows), lanes
@@ -2217,7 +2306,7 @@ RV_DEV void solve_island_fingers_t(Shared& S, const Consts& K, const int X, cons
       for (int x = 0; x < RV_NLIMB; ++x) o[8 + x] = pj[x] * lam;
     }
   }
-  __syncthreads();
+  RV_WAVE_SYNC();
   if (lane < 6 && X >= 0) {
     float acc = e.body[Xc][7 + lane];
     float t[24];
@@ -2256,7 +2345,7 @@ RV_DEV void solve_island_fingers_t(Shared& S, const Consts& K, const int X, cons
     e.q[x] = qn; e.qd[x] = qd;
   }
   if (LIMB && lane == 63) S.s.kin_fresh = 0;
-  __syncthreads();
+  RV_WAVE_SYNC();
 }
 RV_DEV void solve_island_fingers(Shared& S, const Consts& K, const int X, const int with_fingers, const int limb) {
   if (limb) solve_island_fingers_t<true>(S, K, X, with_fingers);
@@ -2622,7 +2711,7 @@ RV_DEV void motors_only_substeps(Shared& S, const Consts& K, const int r) {
   }
   if (mine) { e.q[j] = q; e.qd[j] = qd; S.s.jtravel[j] += trav; }
   if (lane == 0) { e.sim_steps += r; e.substeps_last += r; }
-  __syncthreads();
+  RV_WAVE_SYNC();
 }
 #else
 #define RV_EMU_SECTION 4
@@ -3045,7 +3134,7 @@ RV_DEV int coast_fused(Shared& S, const Consts& K, const int steps_check, const 
     }
   }
   if (lane == 0) S.s.fused_pending = pending;
-  __syncthreads();
+  RV_WAVE_SYNC();
 #else
 #define RV_EMU_SECTION 5
 #include "../../tests/emu/rv_emu_hooks.h"      // host lane emulation (test scaffolding; not compiled into the product)
@@ -3446,11 +3535,14 @@ RV_DEV void sim_substep_heavy(Shared& S, const Consts& K) {
   //      one lane per (body, collider box): bounding-sphere / box proximity;
   //  (1) one lane per owner: drop broken points, motion gate -> does the owner run convex
   //      queries in this substep?
-  //  (2) lane 0: the compact list of owners that do;
-  //  (3) the wave splits into four 16-lane groups that take owners off the list.  All lanes
-  //      of a group execute the same scalar program redundantly -- except inside support_v(),
+  //  (2) the compact list of owners that do, and where the convex pairs of each start in the flat list of
+  //      items (owner, pair): owner order, then pair order;
+  //  (3) the wave splits into four 16-lane groups.  In round r group g runs the QUERY of item 4r + g
+  //      (collide_query: the pairs of one owner run side by side) and stages what it found; then the
+  //      staged results are APPLIED (collide_apply), those of one manifold by one group in pair order
+  //      -- the state of a manifold after each pair is what one group working through the owner gives.
+  //      All lanes of a group execute the same scalar program redundantly -- except inside support_v(),
   //      where each lane holds one hull vertex and a DPP all-reduce picks the extreme one.
-  //      Every convex pair of every owner goes through ONE collide_pair call site.
   RV_LANES_BEGIN
     const DevEnv& e = S.e;
     if (lane < RV_NMAN * 4) {
@@ -3475,7 +3567,7 @@ RV_DEV void sim_substep_heavy(Shared& S, const Consts& K) {
   RV_LANES_END
   RV_LANES_BEGIN
     DevEnv& e = S.e;
-    int runs = 0;
+    int n_all = 0, near0 = 0, near1 = 0;      // this owner's convex pairs; (body, box) proximity flags of this lane
     if (lane < RV_NMAN + RV_NCOL) {
       const int owner = lane;
       OwnerInfo o;
@@ -3500,8 +3592,10 @@ RV_DEV void sim_substep_heavy(Shared& S, const Consts& K) {
         if (run) acc = 0.0f; else n_pairs = 0;
         m.acc = acc;
       }
-      S.s.ow_run[owner] = n_pairs > 0;
-      runs = n_pairs > 0;
+#if !RV_ON_DEVICE
+      S.s.ow_run[owner] = n_pairs;
+#endif
+      n_all = n_pairs;
       if (n_pairs > 0 && o.role >= 0 && o.role <= 2) { S.s.wvneed[o.a] = 1; if (o.b >= 0) S.s.wvneed[o.b] = 1; }
     }
     if (lane >= RV_NMAN + RV_NCOL && lane < RV_NMAN + RV_NCOL + RV_MAXB * RV_NCOL / 2) {
@@ -3514,25 +3608,56 @@ RV_DEV void sim_substep_heavy(Shared& S, const Consts& K) {
           near = !(sphere_aabb_dist2(ld3(e.body[b]), S.s.colmin[col], S.s.colmax[col]) >= r * r);
         }
         S.s.cn[b][col] = near;
+        if (t & 1) near1 = near; else near0 = near;
       }
     }
 #if RV_ON_DEVICE
     {
-      // the compact list of owners that run, in owner order
-      const unsigned long long mk = __builtin_amdgcn_ballot_w64(runs != 0);
-      if (runs) S.s.olist[__builtin_popcountll(mk & ((1ull << lane) - 1ull))] = lane;
-      if (lane == 0) S.s.n_olist = __builtin_popcountll(mk);
+      // (every ballot here is taken by all 64 lanes: the lanes without an owner / a proximity pair hold zeros)
+      // an arm-body owner runs the pairs of the boxes near its body only: the flags of body b sit on the five lanes
+      // from RV_NMAN + RV_NCOL + 5 b, even boxes in near0, odd ones in near1
+      static_assert(RV_NCOL == 10, "five proximity lanes per body");
+      const unsigned long long k0 = __builtin_amdgcn_ballot_w64(near0 != 0), k1 = __builtin_amdgcn_ballot_w64(near1 != 0);
+      int cnt = n_all;
+      if (lane >= RV_MAXB + RV_NBB && lane < RV_NMAN) {
+        const int sh = RV_NMAN + RV_NCOL + 5 * (lane - RV_MAXB - RV_NBB);
+        const int n_near = __builtin_popcount((unsigned)(k0 >> sh) & 31u) + __builtin_popcount((unsigned)(k1 >> sh) & 31u);
+        cnt = (n_all / RV_NCOL) * n_near;
+      }
+      // the compact list of owners that run, in owner order, and the prefix sum of their pair counts (bit by bit)
+      static_assert(RV_NCOL * RV_MAXH < 64 && RV_MAXH * RV_MAXH < 64, "an owner's pair count has six bits");
+      const unsigned long long below = (1ull << lane) - 1ull;
+      const unsigned long long mk = __builtin_amdgcn_ballot_w64(cnt != 0);
+      int first = 0, total = 0;
+#pragma unroll
+      for (int bit = 0; bit < 6; ++bit) {
+        const unsigned long long mb = __builtin_amdgcn_ballot_w64(((cnt >> bit) & 1) != 0);
+        first += __builtin_popcountll(mb & below) << bit;
+        total += __builtin_popcountll(mb) << bit;
+      }
+      if (cnt) S.s.olist[__builtin_popcountll(mk & below)] = lane + 256 * first;
+      if (lane == 0) { S.s.n_olist = __builtin_popcountll(mk); S.s.n_items = total; }
+      if (lane < 4) S.s.pairs[lane] = lane == 0 ? total : 0;
     }
 #else
-    (void)runs;
+    (void)n_all; (void)near0; (void)near1;
 #endif
   RV_LANES_END
 #if !RV_ON_DEVICE
   RV_LANES_BEGIN
     if (lane == 0) {
-      int n = 0;
-      for (int o = 0; o < RV_NMAN + RV_NCOL; ++o) if (S.s.ow_run[o]) S.s.olist[n++] = o;
-      S.s.n_olist = n;
+      int n = 0, first = 0;
+      for (int o = 0; o < RV_NMAN + RV_NCOL; ++o) {
+        int cnt = S.s.ow_run[o];
+        if (o >= RV_MAXB + RV_NBB && o < RV_NMAN) {
+          int n_near = 0;
+          for (int col = 0; col < RV_NCOL; ++col) n_near += S.s.cn[o - RV_MAXB - RV_NBB][col] != 0;
+          cnt = (cnt / RV_NCOL) * n_near;
+        }
+        if (cnt) { S.s.olist[n++] = o + 256 * first; first += cnt; }
+      }
+      S.s.n_olist = n; S.s.n_items = first;
+      S.s.pairs[0] = first; S.s.pairs[1] = 0; S.s.pairs[2] = 0; S.s.pairs[3] = 0;
     }
   RV_LANES_END
 #endif
@@ -3572,51 +3697,74 @@ RV_DEV void sim_substep_heavy(Shared& S, const Consts& K) {
     }
   }
   RV_PROF(18)
-  RV_LANES_BEGIN
-    DevEnv& e = S.e;
-    const int slot = lane >> 4;
+  {
+    const int n_items = RV_UNI(S.s.n_items), n_list = RV_UNI(S.s.n_olist);
+    // where the group's item lies in olist: items only go up, so the search goes on from the last find
+    // (host emulation: one cursor per group, held by the one lane of the group that works)
+    int cur_[RV_ON_DEVICE ? 1 : 4] = {};
+    for (int i0 = 0; i0 < n_items; i0 += 4) {
+      RV_LANES_BEGIN
+        const int slot = lane >> 4;
 #if !RV_ON_DEVICE
-    if ((lane & 15) != 0) continue;   // host emulation: one lane per group does the work
+        if ((lane & 15) != 0) continue;   // host emulation: one lane per group does the work
 #endif
-    RV_PROFG(5)   // (profiling build) time outside the narrow phase goes to a dump slot
-    int my_pairs = 0;
-    const int n_list = S.s.n_olist;
-    for (int idx = slot; idx < n_list; idx += 4) {
-      const int owner = S.s.olist[idx];
-      OwnerInfo o;
-      owner_decode(S, K, owner, arm_on, o);
-      const int role = o.role, a = o.a, b = o.b, mi = o.mi, n_inner = o.n_inner;
-      const int n_pairs = o.n_outer * o.n_inner;
-      for (int t = 0; t < n_pairs; ++t) {
-        int io = t / n_inner, ii = t - io * n_inner;
-        const float* A; const float* B; int nA, nB, ckind, col = -1;
-        v3 guess = o.guess0;
-        if (role == 0) { A = &S.s.u.r.wv[a][ii][0][0]; nA = S.n_verts[a][ii]; B = body_below_table(e, c, a) ? &S.s.groundv[0][0] : &S.s.tablev[0][0]; nB = 8; ckind = 0; }
-        else if (role == 1) { A = &S.s.u.r.wv[a][io][0][0]; nA = S.n_verts[a][io]; B = &S.s.u.r.wv[b][ii][0][0]; nB = S.n_verts[b][ii]; ckind = 1; }
-        else if (role == 2) {
-          col = io;
-          if (!S.s.cn[a][col]) continue;
-          A = &S.s.u.r.wv[a][ii][0][0]; nA = S.n_verts[a][ii]; B = &S.s.colv[col][0][0]; nB = 8; ckind = 2;
-          guess = sub(ld3(e.body[a]), ld3(S.s.colc[col]));
-        } else { col = a; A = &S.s.colv[col][0][0]; nA = 8; B = &S.s.tablev[0][0]; nB = 8; ckind = 0; }
-        float dd;
-        my_pairs++;
+        RV_PROFG(5)   // (profiling build) time outside the queries goes to a dump slot
+        const int i = i0 + slot;
+        if (i < n_items) {
+          int& cur = cur_[RV_ON_DEVICE ? 0 : slot];
+          while (cur + 1 < n_list && (S.s.olist[cur + 1] >> 8) <= i) ++cur;
+          const int owner = S.s.olist[cur] & 255, k = i - (S.s.olist[cur] >> 8);
+          PairItem p;
+          item_decode(S, K, owner, k, p);
 #ifdef RV_DEBUG_PAIRS
-        fprintf(stderr, "P %d %d %d %d %d\n", e.sim_steps, ckind, role == 3 ? 0 : a, b, col);
+          fprintf(stderr, "P %d %d %d %d %d\n", S.e.sim_steps, p.ckind, p.a, p.b, p.col);
 #endif
-        const float brk = role == 3 ? brk_col(arm, c, col) : brk_of(e, arm, c, ckind, a, b, col);
-        // which pair of hulls of the manifold (the key of its simplex cache)
-        const int pair = role == 0 ? ii + (body_below_table(e, c, a) ? 64 : 0) : (role == 1 ? io * 8 + ii : (role == 2 ? col * 8 + ii : 0));
-        int hit = collide_pair(S, K, ckind, role == 3 ? 0 : a, b, col, A, nA, B, nB, guess, role == 3 ? nullptr : &e.man[mi], &dd, brk, pair);
-        if (role == 3 && hit && dd < c->contact_query_dist) S.s.colflag[col] = 1;
+          // the simplex cache the query sees: the first pair of the pass reads what the last pass left; a later one would
+          // find the cache empty or under another pair's key -- a miss either way.  Nothing is written to the manifold here
+          GjkCache gc;
+          gc.n = 0; gc.pair = 0;
+#pragma unroll
+          for (int x = 0; x < 3; ++x) { gc.ia[x] = 0; gc.ib[x] = 0; }
+          if (p.role != 3 && k == 0) gc = S.e.man[p.mi].gc;
+          QStage st;
+          collide_query(K, p, p.role == 3 ? nullptr : &gc, st);
+          QStage& o = S.s.qst[slot];
+          o.hit = st.hit; o.gc = st.gc;
+          if (st.hit) {
+            o.d = st.d;
+#pragma unroll
+            for (int x = 0; x < 3; ++x) { o.n[x] = st.n[x]; o.pa[x] = st.pa[x]; o.pb[x] = st.pb[x]; }
+          }
+          if (p.role == 3 && st.hit && st.d < c->contact_query_dist) S.s.colflag[p.col] = 1;
 #ifdef RV_EMU_COUNT
-        // queries by role; of them: no contact found (separation beyond the breaking distance)
-        rv_emu_dbg2[40 + role] += 1; if (!hit) rv_emu_dbg2[44 + role] += 1;
+          // queries by role; of them: no contact found (separation beyond the breaking distance)
+          rv_emu_dbg2[40 + p.role] += 1; if (!st.hit) rv_emu_dbg2[44 + p.role] += 1;
 #endif
-      }
+        }
+      RV_LANES_END
+      RV_LANES_BEGIN
+        const int slot = lane >> 4;
+#if !RV_ON_DEVICE
+        if ((lane & 15) != 0) continue;
+#endif
+        const int i = i0 + slot;
+        if (i < n_items) {
+          const int cur = cur_[RV_ON_DEVICE ? 0 : slot];
+          const int first = S.s.olist[cur] >> 8;
+          const int owner = S.s.olist[cur] & 255, k = i - first;
+          const int n_own = (cur + 1 < n_list ? (S.s.olist[cur + 1] >> 8) : n_items) - first;
+          // the results of one manifold are applied by the group that holds the first of them in this round, in pair order
+          if (owner < RV_NMAN && (slot == 0 || k == 0)) {
+            for (int x = 0; slot + x < 4 && k + x < n_own; ++x) {
+              PairItem p;
+              item_decode(S, K, owner, k + x, p);
+              collide_apply(S, K, p, &S.e.man[p.mi], S.s.qst[slot + x]);
+            }
+          }
+        }
+      RV_LANES_END
     }
-    if ((lane & 15) == 0) S.s.pairs[slot] = my_pairs;
-  RV_LANES_END
+  }
 
   RV_STOP(3)
   RV_PROF(3)
@@ -3771,9 +3919,9 @@ RV_DEV void sim_substep_heavy(Shared& S, const Consts& K) {
     {
       SerialRows SR;
       serial_rows_setup(S, K, limb, SR);
-      __syncthreads();
+      RV_WAVE_SYNC();
       solve_with_fingers(S, K, limb, SR);      // (every lane: see SerialRows)
-      __syncthreads();
+      RV_WAVE_SYNC();
     }
 #else
     RV_LANES_BEGIN
@@ -3853,7 +4001,7 @@ RV_DEV void sim_substep_heavy(Shared& S, const Consts& K) {
       row_setup(S, K, kind, a, b, pt, my, m.n);          // (lanes without a point compute a row nobody asks for)
       if (use) { m.ln[i] = m.ln[i] * c->warmstart; m.lt1[i] = m.lt1[i] * c->warmstart; m.lt2[i] = m.lt2[i] * c->warmstart; }
     }
-    __syncthreads();
+    RV_WAVE_SYNC();
     auto pull = [&](float x, int src) { return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(src << 2, __builtin_bit_cast(int, x))); };
     auto pull_row = [&](int src, bool pair) {
       Row r;
@@ -3908,7 +4056,7 @@ RV_DEV void sim_substep_heavy(Shared& S, const Consts& K) {
         if (active) st_bv(e, b, A);
         if (lane < RV_MAXB) S.s.res[lane] = res;
       }
-      __syncthreads();
+      RV_WAVE_SYNC();
       for (int rd = 0; rd < 3; ++rd) {
         const int x = lane < 2 ? lane : 0;
         const int k = bb_round_pair(rd, x);
@@ -3935,7 +4083,7 @@ RV_DEV void sim_substep_heavy(Shared& S, const Consts& K) {
         }
         if (active) { st_bv(e, a_, A); st_bv(e, b_, B); }
         if (lane < 2) S.s.res[4 + 2 * rd + lane] = res;
-        __syncthreads();
+        RV_WAVE_SYNC();
       }
       float res = 0.0f;
 #pragma unroll
@@ -3943,7 +4091,7 @@ RV_DEV void sim_substep_heavy(Shared& S, const Consts& K) {
       res = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, res)));
       if (it >= 0 && res < big_tol) break;
       if (it >= 0 && c->solver_stall > 0) { if (res < big_best) { big_best = res; big_since = 0; } else if (++big_since >= c->solver_stall) break; }
-      __syncthreads();          // (S.s.res is written again by the next sweep)
+      RV_WAVE_SYNC();          // (S.s.res is written again by the next sweep)
     }
   }
 #else
@@ -4085,7 +4233,7 @@ RV_DEV void sim_substep_heavy(Shared& S, const Consts& K) {
     }
 #if RV_ON_DEVICE
   }
-  __syncthreads();
+  RV_WAVE_SYNC();
 #else
   RV_LANES_END
   }

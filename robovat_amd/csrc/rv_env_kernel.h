@@ -74,7 +74,7 @@ template <int TMODE>
 #else
 #define RV_ENV_OCC
 #endif
-__global__ __launch_bounds__(64) RV_ENV_OCC void k_env(EnvKernelArgs args) {
+__global__ __launch_bounds__(RV_ENV_THREADS) RV_ENV_OCC void k_env(EnvKernelArgs args) {
   const int MODE = TMODE >= 0 ? TMODE : args.mode;
   Shared& S = g_shared;
   const bool queued = TMODE < 0 && args.q_slots != nullptr;      // (the run-time-dispatched instantiation only)

@@ -13,6 +13,6 @@ int main() {
   F(limb_dv) F(limb_vt) F(limb_qd0) F(lcom) F(lA) F(lGq) F(llo) F(lhi) F(ltgt) F(lJa) F(lMiJ) F(linvk) F(jmoving) F(jchg) F(rvec)
   F(jt_applied) F(atflag) F(kin_fresh) F(ftravel) F(far_valid) F(far_n) F(far) F(nearf) F(bnear) F(near_any) F(sep) F(coltravel)
   F(cdelta) F(clr_t) F(clr_b) F(clr_valid) F(jtravel) F(ccoef) F(crun) F(fused_n) F(fused_pending) F(coast_unsafe) F(jlen) F(colext)
-  F(fext) F(fmot) F(any_on) F(pairs) F(rf_dist) F(rf_rm) F(cn) F(ow_run) F(olist) F(n_olist) F(wvneed) F(rng)
+  F(fext) F(fmot) F(any_on) F(pairs) F(rf_dist) F(rf_rm) F(cn) F(ow_run) F(olist) F(n_olist) F(n_items) F(qst) F(wvneed) F(rng)
   printf("%5zu words\n", sizeof(Scratch) / 4);
 }
