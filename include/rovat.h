@@ -314,6 +314,11 @@ const char* rv_last_error(void);
 int  rv_set_stream(rv_world* w, void* hip_stream);
 int  rv_synchronize(rv_world* w);
 int  rv_num_envs(const rv_world* w);
+/* which build of the env kernel this world launches (chosen once, in rv_create): RV_ENV_BUILD_OCC1 = k_env (all
+ * registers, one wave per SIMD), RV_ENV_BUILD_OCC2 = k_env_occ2 (256 registers, two waves per SIMD); 0 for NULL */
+#define RV_ENV_BUILD_OCC1 1
+#define RV_ENV_BUILD_OCC2 2
+int  rv_env_kernel_build(const rv_world* w);
 
 /* ---- RobotEnv.reset (robot_env.py:204-237) = PushEnv._reset_scene +
  *      _load_movable_bodies + _sample_body_poses(_on_tiles) (push_env.py:331-597)

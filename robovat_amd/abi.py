@@ -36,6 +36,8 @@ RV_CP_TABLE = RV_MAXB
 RV_CP_ARM = RV_MAXB + 1
 RV_CP_MAX = RV_NMAN * 4 + 1
 RV_NCOUNTERS = 10
+# rv_env_kernel_build: the build of the env kernel a world launches (k_env / k_env_occ2)
+RV_ENV_BUILD_OCC1, RV_ENV_BUILD_OCC2 = 1, 2
 
 RV_OK, RV_ERR_VALUE, RV_ERR_STATE, RV_ERR_HIP, RV_ERR_NOTIMPL = 0, 1, 2, 3, 4
 RV_TASK_NONE, RV_TASK_CLEARING, RV_TASK_INSERTION, RV_TASK_CROSSING = 0, 1, 2, 3

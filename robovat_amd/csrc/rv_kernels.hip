@@ -768,6 +768,7 @@ int rv_destroy(rv_world* w) {
 int rv_set_stream(rv_world* w, void* s) { WCHK(w); w->stream = (hipStream_t)s; return RV_OK; }
 int rv_synchronize(rv_world* w) { WCHK(w); HIPCHK(hipStreamSynchronize(w->stream)); return RV_OK; }
 int rv_num_envs(const rv_world* w) { return w ? w->n : 0; }
+int rv_env_kernel_build(const rv_world* w) { return !w ? 0 : w->occ2 ? RV_ENV_BUILD_OCC2 : RV_ENV_BUILD_OCC1; }
 
 int rv_reset(rv_world* w, const uint8_t* d_env_mask) { WCHK(w); return launch_env<MODE_RESET>(w, d_env_mask, 0, 0, 0, 0, 0, 0); }
 int rv_step_macro(rv_world* w) { WCHK(w); return launch_env<MODE_MACRO>(w, nullptr, 0, 0, 0, 0, 0, 0); }

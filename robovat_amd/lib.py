@@ -32,7 +32,7 @@ SYMBOLS = [
     'rv_reset_targets', 'rv_get_state_ptrs', 'rv_source_hash', 'rv_set_motor_targets', 'rv_grip',
     'rv_rollout_record', 'rv_render', 'rv_set_gravity', 'rv_rollout_record_full', 'rv_step_begin', 'rv_step_poll', 'rv_set_constraint', 'rv_render_rgb', 'rv_set_friction', 'rv_set_auto_reset',
     'rv_set_constraint_ex', 'rv_set_link_path', 'rv_get_robot_ready', 'rv_get_camera', 'rv_set_max_joint_velocities',
-    'rv_policy_antipodal', 'rv_get_contact_points',
+    'rv_policy_antipodal', 'rv_get_contact_points', 'rv_env_kernel_build',
 ]
 
 _EXC = {abi.RV_ERR_VALUE: ValueError, abi.RV_ERR_STATE: RuntimeError,
@@ -131,6 +131,7 @@ def load():
     lib.rv_set_stream.argtypes = [vp, vp]
     lib.rv_synchronize.argtypes = [vp]
     lib.rv_num_envs.argtypes = [vp]
+    lib.rv_env_kernel_build.argtypes = [vp]
     lib.rv_reset.argtypes = [vp, vp]
     lib.rv_step_macro.argtypes = [vp]
     lib.rv_step_sub.argtypes = [vp, i32]
@@ -272,6 +273,10 @@ class World(object):
 
     def synchronize(self):
         check(self.lib.rv_synchronize(self.h))
+
+    def env_kernel_build(self):
+        """rv_env_kernel_build: abi.RV_ENV_BUILD_OCC1 (k_env) or abi.RV_ENV_BUILD_OCC2 (k_env_occ2), as rv_create chose."""
+        return int(self.lib.rv_env_kernel_build(self.h))
 
     # -- env stepping
     def reset(self, mask=None):

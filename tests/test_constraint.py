@@ -8,8 +8,9 @@ import pytest
 from robovat_amd import abi, configs, scenes
 
 import test_kat_contact as T
+from test_kat_contact import close_hip_worlds  # noqa: F401  (closes the worlds of the HIP backends)
 
-BACKENDS = ['oracle64', 'oracle32', pytest.param('hip', marks=pytest.mark.gpu)]
+BACKENDS = T.BACKENDS          # both precisions of the oracle and both builds of the env kernel
 Q0 = (0, 0, 0, 1)
 
 

@@ -14,18 +14,34 @@ from robovat_amd import abi, configs, scenes
 EMU_DIR = os.path.join(os.path.dirname(__file__), 'emu')
 
 
-@pytest.fixture(scope='module')
-def emu():
-    so = os.path.join(EMU_DIR, 'librv_emu.so')
+EMU_FLAGS = ['-O2', '-std=c++17', '-fPIC', '-ffp-contract=off', '-mfma', '-fopenmp', '-shared']
+# the two arrangements of env_program's segments (rv_dev_env.h): inlined, as rv_kernels.hip compiles them, and behind
+# the out-of-line seg_* wrappers of rv_kernels_occ2.hip (RV_SEGMENTS_NOINLINE)
+ARRANGEMENTS = {'inline': ('librv_emu.so', []), 'seg': ('librv_emu_seg.so', ['-DRV_SEGMENTS_NOINLINE=1'])}
+
+
+def emu_library(arrangement='inline'):
+    """The lane emulator in one arrangement, compiled when it is missing or older than one of its sources."""
+    name, defines = ARRANGEMENTS[arrangement]
+    so = os.path.join(EMU_DIR, name)
     src = os.path.join(EMU_DIR, 'rv_emu.cpp')
     csrc = os.path.join(EMU_DIR, '..', '..', 'robovat_amd', 'csrc')
     deps = [src, os.path.join(EMU_DIR, 'rv_emu_hooks.h')] + [os.path.join(csrc, n) for n in ('rv_dev_env.h', 'rv_dev_collide.h', 'rv_dev_math.h')]
     if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        subprocess.run(['g++', '-O2', '-std=c++17', '-fPIC', '-ffp-contract=off', '-mfma', '-fopenmp', '-shared', src, '-o', so], check=True)
+        subprocess.run(['g++'] + EMU_FLAGS + defines + [src, '-o', so], check=True)
     lib = C.CDLL(so)
     lib.emu_create.restype = C.c_void_p
     lib.emu_create.argtypes = [C.POINTER(abi.rv_config), C.POINTER(abi.rv_scene)]
     return lib
+
+
+@pytest.fixture(scope='module')
+def emu():
+    """The lane emulator with the segments of the env program inlined.  Every test that takes this fixture runs a second
+    time in tests/test_emu_parity_seg.py, which overrides it with the 'seg' arrangement (segments behind the seg_*
+    wrappers of the two-waves-per-SIMD build).  On the host RV_DEV_NOINLINE is `static`, so that second run checks what the
+    wrappers forward and rebuild, not registers or scratch."""
+    return emu_library('inline')
 
 
 class Emu(object):

@@ -103,6 +103,7 @@ def test_recorded_rollout_on_the_two_waves_per_simd_build(rollout_ref):
     import torch
     n = 4 * torch.cuda.get_device_properties(0).multi_processor_count + 1
     world = _world(n, 5)
+    assert world.env_kernel_build() == 2
     world.reset()
     world.rollout_record(3, auto_reset=True, point_cloud=False)
     _cmp(world, rollout_ref)

@@ -291,6 +291,7 @@ def test_both_builds_of_the_env_kernel_match_the_oracle(monkeypatch):
     for occ in ('1', '2'):
         monkeypatch.setenv('RV_ENV_OCC', occ)
         w = lib.World(cfg, scene, device=0)
+        assert w.env_kernel_build() == int(occ)
         w.reset(); w.rollout(5, first_macro_index=0, auto_reset=True, record=False)
         assert np.array_equal(w.body_state().cpu().numpy(), ref.body_state().astype(np.float32)), occ
         assert np.array_equal(w.joint_state().cpu().numpy(), ref.joint_state().astype(np.float32)), occ

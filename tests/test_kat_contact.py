@@ -33,15 +33,40 @@ class _Np(object):
         return call
 
 
-BACKENDS = ['oracle64', 'oracle32', pytest.param('hip', marks=pytest.mark.gpu)]
+# 'hip': the build of the env kernel rv_create picks for a world this small (k_env); 'hip_occ2': the same world on the
+# 256-register build every world with more envs than SIMDs launches (k_env_occ2, forced through RV_ENV_OCC)
+HIP_BUILDS = {'hip': abi.RV_ENV_BUILD_OCC1, 'hip_occ2': abi.RV_ENV_BUILD_OCC2}
+BACKENDS = ['oracle64', 'oracle32', pytest.param('hip', marks=pytest.mark.gpu), pytest.param('hip_occ2', marks=pytest.mark.gpu)]
+
+
+_OPEN = []
+
+
+@pytest.fixture(autouse=True)
+def close_hip_worlds():
+    """Every lib.World a test made through _hip_world is closed when the test ends, passed or failed (the modules that
+    import _hip_world import this fixture as well)."""
+    yield
+    while _OPEN:
+        _OPEN.pop().close()
+
+
+def _hip_world(backend, cfg, scene):
+    """The lib.World of a HIP backend, numpy in / numpy out, on the build of the env kernel the backend names."""
+    from robovat_amd import lib
+    with pytest.MonkeyPatch.context() as mp:
+        mp.setenv('RV_ENV_OCC', str(HIP_BUILDS[backend]))
+        w = lib.World(cfg, scene, device=0)
+    _OPEN.append(w)
+    assert w.env_kernel_build() == HIP_BUILDS[backend]
+    return _Np(w)
 
 
 def _world(backend, n=1, **over):
     scene, names = scenes.make_scene()
     cfg = configs.make_rv_config(env_cfg=configs.push_env_config(**over), n_envs=n, seed=1, shape_names=names)
-    if backend == 'hip':
-        from robovat_amd import lib
-        return _Np(lib.World(cfg, scene, device=0)), cfg
+    if backend in HIP_BUILDS:
+        return _hip_world(backend, cfg, scene), cfg
     from oracle import orc
     return orc.OracleWorld(cfg, scene, double=(backend == 'oracle64')), cfg
 

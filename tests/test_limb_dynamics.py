@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 
 from robovat_amd import abi, configs, scenes
-from test_kat_contact import BACKENDS, _Np
+from test_kat_contact import BACKENDS, HIP_BUILDS, _hip_world, close_hip_worlds  # noqa: F401
 
 G = 9.8
 
@@ -24,9 +24,8 @@ def _world(backend, limb=1, n=1):
     scene, names = scenes.make_scene()
     cfg = configs.make_rv_config(env_cfg=configs.push_env_config(**{'PHYSICS.LIMB_DYNAMICS': limb}),
                                  n_envs=n, seed=1, shape_names=names)
-    if backend == 'hip':
-        from robovat_amd import lib
-        return _Np(lib.World(cfg, scene, device=0)), cfg, scene
+    if backend in HIP_BUILDS:
+        return _hip_world(backend, cfg, scene), cfg, scene
     from oracle import orc
     return orc.OracleWorld(cfg, scene, double=(backend == 'oracle64')), cfg, scene
 

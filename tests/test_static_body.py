@@ -18,7 +18,8 @@ import pytest
 
 from robovat_amd import abi, configs, scenes
 
-from test_kat_contact import BACKENDS, Q0, _Np, _bodies     # noqa: F401
+from test_kat_contact import BACKENDS, HIP_BUILDS, Q0, _bodies, _hip_world, close_hip_worlds     # noqa: F401
+from test_emu_parity import emu     # noqa: F401  (the lane emulator's fixture; tests/test_emu_parity_seg.py runs the test below on the other arrangement)
 
 WALL_HALF = (0.02, 0.65, 0.4)       # scenes.default_shape_hulls: 'wall'
 BOX_HALF_X = 0.035
@@ -27,9 +28,8 @@ BOX_HALF_X = 0.035
 def _world(backend, n=1, **over):
     scene, names = scenes.make_scene()
     cfg = configs.make_rv_config(env_cfg=configs.push_env_config(**over), n_envs=n, seed=1, shape_names=names)
-    if backend == 'hip':
-        from robovat_amd import lib
-        return _Np(lib.World(cfg, scene, device=0)), cfg, names
+    if backend in HIP_BUILDS:
+        return _hip_world(backend, cfg, scene), cfg, names
     from oracle import orc
     return orc.OracleWorld(cfg, scene, double=(backend == 'oracle64')), cfg, names
 
@@ -114,16 +114,10 @@ def _throw_at_the_wall(cfg, st, par):
 
 
 @pytest.mark.parametrize('over', WALLS)
-def test_emulated_kernel_with_a_wall_is_bit_exact_vs_float_oracle(over):
+def test_emulated_kernel_with_a_wall_is_bit_exact_vs_float_oracle(emu, over):  # noqa: F811
     import test_emu_parity as T
     from oracle import orc
-    import os, subprocess
-    so = os.path.join(T.EMU_DIR, 'librv_emu.so')
-    if not os.path.exists(so):
-        subprocess.run(['g++', '-O2', '-std=c++17', '-fPIC', '-ffp-contract=off', '-mfma', '-fopenmp', '-shared', os.path.join(T.EMU_DIR, 'rv_emu.cpp'), '-o', so], check=True)
-    lib = C.CDLL(so)
-    lib.emu_create.restype = C.c_void_p
-    lib.emu_create.argtypes = [C.POINTER(abi.rv_config), C.POINTER(abi.rv_scene)]
+    lib = emu
     scene, names = scenes.make_scene()
     cfg = configs.make_rv_config(env_cfg=configs.push_env_config(**over), n_envs=6, seed=17, shape_names=names)
     ref = orc.OracleWorld(cfg, scene, double=False)
@@ -169,6 +163,7 @@ def test_hip_with_a_wall_matches_float_oracle_bit_for_bit(over, occ, monkeypatch
     monkeypatch.setenv('RV_ENV_OCC', occ)
     from test_gpu_parity import _worlds, _cmp
     world, ref, cfg = _worlds(32, seed=9, **over)
+    assert world.env_kernel_build() == int(occ)
     world.reset(); ref.reset()
     assert _cmp(world, ref, 0.0) == 0.0
     wall = ref.body_state()[:, abi.RV_MAXB - 1].astype(np.float32).copy()
