@@ -208,7 +208,7 @@ struct Scratch {
   int num_waypoints, interrupt, has_budget, max_phase_steps;
   int loop_break, wus_steps, wus_stable, valid;
   int wake[RV_MAXB];
-  // budget of the running sim_run_call (rv_step_poll): at most bud_sub substeps / bud_clk shader
+  // budget of the running sim_run (rv_step_poll): at most bud_sub substeps / bud_clk shader
   // clocks from bud_t0 in this launch (0 = no limit); suspended: the call returned on the budget
   int bud_sub, bud_sub0, suspended, wus_resume;
   unsigned long long bud_clk, bud_t0;
@@ -272,9 +272,8 @@ struct Scratch {
 struct Shared {
   DevEnv e;
   Scratch s;
-  // launch constants staged in LDS: inside the out-of-line substep a pointer
-  // argument is not provably wave-uniform, so reading rv_config / rv_arm
-  // through it would be a vector global load (L2 latency) per field
+  // launch constants staged in LDS: a pointer argument is not provably wave-uniform, so reading
+  // rv_config / rv_arm through it would be a vector global load (L2 latency) per field
   rv_config cfg;
   rv_arm arm;
   int n_hulls[RV_MAXB];
@@ -3164,7 +3163,7 @@ RV_DEV void arm_refresh_kinematics(Shared& S, const Consts& K) {
 }
 // up to `want` coasted substeps with the fused loop; the kinematics are measured again whenever the
 // clearance is used up (fresh clearances that buy nothing: close to something -> the caller steps)
-RV_DEV int coast_run_body(Shared& S, const Consts& K, const int steps_check, const int want, int* why_out) {
+RV_DEV int coast_run(Shared& S, const Consts& K, const int steps_check, const int want, int* why_out) {
   int why = 0, n = 0;
   for (;;) {
     n += coast_fused(S, K, steps_check, want - n, &why);
@@ -3180,23 +3179,6 @@ RV_DEV int coast_run_body(Shared& S, const Consts& K, const int steps_check, con
   *why_out = why;
   return n;
 }
-#if defined(RV_COAST_NOINLINE) && RV_ON_DEVICE
-// A build variant of the 256-register kernel (RV_OCC2_COAST_OUT_OF_LINE, off): the coasting run as a function of its own.
-// Inlined into the substep loop its hottest loops -- one iteration per coasted substep, 97 % of all substeps -- carry reloads of
-// values the surrounding code pushed out to scratch (-Rpass-missed=regalloc: 22 + 4 + 1 reloads in the three nested loops of
-// coast_fused, 49 in this one); as a callee it is allocated by itself and those loops are clean -- but a run of coasted
-// substeps is short (tens of substeps) and the save / restore of the caller's live registers per call costs more than the
-// reloads did: measured - 9 % on config 5, - 11 % on config 4 (profiles/r06_k_occ2_coast_out_of_line.txt).  (n < 2^28; why in the top bits)
-RV_DEV_NOINLINE int coast_run_fn(const rv_scene* scene, int stop_after, int steps_check, int want);      // (defined below g_shared)
-RV_DEV int coast_run(Shared& S, const Consts& K, const int steps_check, const int want, int* why_out) {
-  (void)S;
-  const int r = coast_run_fn(K.scene, K.stop_after, steps_check, want);
-  *why_out = (int)((unsigned)r >> 28);
-  return r & 0x0fffffff;
-}
-#else
-RV_DEV int coast_run(Shared& S, const Consts& K, const int steps_check, const int want, int* why_out) { return coast_run_body(S, K, steps_check, want, why_out); }
-#endif
 
 // link twist of frame f (used by the arm-body contact rows; base is static): w_f = sum_k axis_k qd_k,
 // v_f = sum_k (axis_k qd_k) x (p_f - p_k) over the joints upstream of f; the fingers add their slide along
@@ -3236,12 +3218,7 @@ RV_DEV int sim_substep_light(Shared& S, const Consts& K) {
   // needs the frames (kin_fresh = 0).  Exact: every skipped test would have said "no".  (Without deactivation --
   // the reference's most likely semantics -- the arm is far in ~80 % of the substeps.)
   int far = 0;
-#if !RV_ON_DEVICE
-  static const int rv_no_far = getenv("RV_NO_FAR") != nullptr;     // (host emulation: debugging aid)
-#else
-  const int rv_no_far = 0;
-#endif
-  if (arm_on && K.stop_after == 0 && S.s.far_valid && !rv_no_far && !c->finger_dynamics && !c->limb_dynamics) {
+  if (arm_on && K.stop_after == 0 && S.s.far_valid && !c->finger_dynamics && !c->limb_dynamics) {
     int ok = 0;
 #pragma unroll
     for (int b = 0; b < RV_MAXB; ++b) ok |= body_on(S.e, b);
@@ -3716,9 +3693,6 @@ RV_DEV void sim_substep_heavy(Shared& S, const Consts& K) {
           const int owner = S.s.olist[cur] & 255, k = i - (S.s.olist[cur] >> 8);
           PairItem p;
           item_decode(S, K, owner, k, p);
-#ifdef RV_DEBUG_PAIRS
-          fprintf(stderr, "P %d %d %d %d %d\n", S.e.sim_steps, p.ckind, p.a, p.b, p.col);
-#endif
           // the simplex cache the query sees: the first pair of the pass reads what the last pass left; a later one would
           // find the cache empty or under another pair's key -- a miss either way.  Nothing is written to the manifold here
           GjkCache gc;
@@ -4240,9 +4214,8 @@ RV_DEV void sim_substep_heavy(Shared& S, const Consts& K) {
 #endif
 }
 
-// The env block lives in ONE statically addressed LDS object so that the
-// (large) substep body can be a real function with a single copy in the
-// instruction stream instead of being inlined at every call site.
+// The env block lives in ONE statically addressed LDS object: the out-of-line segments of the two-waves-per-SIMD build
+// (seg_*, below) reach it by name -- through a pointer argument their LDS accesses would be compiled as flat loads.
 #if RV_ON_DEVICE
 __shared__ Shared g_shared;
 #else
@@ -4262,14 +4235,6 @@ RV_DEV Consts lds_consts(const rv_scene* scene, int stop_after) {
   Consts K; K.cfg = &g_shared.cfg; K.arm = &g_shared.arm; K.scene = scene; K.stop_after = stop_after;
   return K;
 }
-#if defined(RV_COAST_NOINLINE) && RV_ON_DEVICE
-RV_DEV_NOINLINE int coast_run_fn(const rv_scene* scene, int stop_after, int steps_check, int want) {
-  const Consts K = lds_consts(scene, stop_after);
-  int why = 0;
-  const int n = coast_run_body(g_shared, K, steps_check, want, &why);
-  return n | (why << 28);
-}
-#endif
 // Simulator.check_stable over a body mask (simulator.py:289-323)
 RV_DEV int bodies_stable(const DevEnv& e, unsigned mask, float lin_thr, float ang_thr) {
   for (int b = 0; b < RV_MAXB; ++b) {
@@ -4286,28 +4251,21 @@ RV_DEV unsigned active_mask(const DevEnv& e) {
 }
 RV_DEV void phase_tick(Shared& S, const Consts& K);
 RV_DEV void gphase_tick(Shared& S, const Consts& K);
-// Runs substeps inside ONE out-of-line function, so that the call overhead
-// (callee-saved registers: ~140 VGPRs saved and restored per call) is paid per call
-// and not per substep, and the light part exists once in the instruction stream.
-//   n_fixed > 0 : exactly n_fixed times Simulator.step
-//   n_fixed == 0: Simulator.wait_until_stable (simulator.py:325-376); mask == 0 => all active
-//   n_fixed < 0 : the phase loop of PushEnv._execute_action (push_env.py:648-719: step
-//                 until the next multiple of STEPS_CHECK, phase_tick, until 'done'),
-//                 followed by its closing wait_until_stable -- one call per env.step()
-#ifdef RV_HEAVY_NOINLINE      // (an option of the two-waves-per-SIMD build: the heavy part as a function of its own)
-RV_DEV_NOINLINE void sim_substep_heavy_fn(const rv_scene* scene, int stop_after) { const Consts K = lds_consts(scene, stop_after); sim_substep_heavy(g_shared, K); }
-RV_DEV void sim_substep_heavy_call(Shared& S, const Consts& K) { (void)S; sim_substep_heavy_fn(K.scene, K.stop_after); }
-#endif
-// What one run of the substep loop is asked to do (the arguments of the former sim_run_call)
+// What one run of the substep loop (sim_run) is asked to do:
+//   n_arg > 0 : exactly n_arg times Simulator.step
+//   n_arg == 0: Simulator.wait_until_stable (simulator.py:325-376); mask == 0 => all active
+//   n_arg < 0 : the phase loop of PushEnv._execute_action (push_env.py:648-719: step
+//               until the next multiple of STEPS_CHECK, phase_tick, until 'done'),
+//               followed by its closing wait_until_stable -- one run per env.step()
 struct RunReq { int n_arg; unsigned mask; float lin_thr, ang_thr; int check_after, min_stable, max_steps; };
 RV_DEV RunReq run_req(int n_arg, unsigned mask = 0u, float lin = 0.0f, float ang = 0.0f, int ca = 0, int ms = 0, int mx = 0) {
   RunReq r; r.n_arg = n_arg; r.mask = mask; r.lin_thr = lin; r.ang_thr = ang; r.check_after = ca; r.min_stable = ms; r.max_steps = mx;
   return r;
 }
 // The substep loop.  It exists ONCE in every env kernel: env_program() -- the reset / env.step() / rollout logic
-// written as a resumable program -- hands it one request after the other from a single call site, so nothing of it
-// is a function call (until round 4 it was an out-of-line function entered per env.step(), and its heavy part a
-// second one entered per awake substep: each call saved and restored ~200 registers through scratch memory).
+// written as a resumable program -- hands it one request after the other from a single call site, so it is inlined into
+// the kernel with both parts of the substep and no call is left on the path to save registers through scratch (with none,
+// the L2 write-outs of a bench launch are down to 57 MB: profiles/r04_final_pmc.txt).
 RV_DEV void sim_run_body(Shared& S, const Consts& K, const RunReq& rq) {
   const rv_scene* scene = K.scene; const int stop_after = K.stop_after; (void)scene; (void)stop_after;
   const int n_arg = rq.n_arg; const unsigned mask = rq.mask; const float lin_thr = rq.lin_thr, ang_thr = rq.ang_thr;
@@ -4456,11 +4414,7 @@ RV_DEV void sim_run_body(Shared& S, const Consts& K, const RunReq& rq) {
     if (sim_substep_light(S, K)) {
       RV_CNT(10, 1)
       RV_PROF(1)
-#ifdef RV_HEAVY_NOINLINE
-      sim_substep_heavy_call(S, K);
-#else
       sim_substep_heavy(S, K);
-#endif
       RV_PROF(6)
     } else {
       RV_PROF(0)
@@ -4500,22 +4454,9 @@ RV_DEV void sim_run_body(Shared& S, const Consts& K, const RunReq& rq) {
     RV_LANES_END
   }
 }
-#ifdef RV_SIM_RUN_NOINLINE
-// The two-waves-per-SIMD build keeps the loop as ONE function (a boundary for the register allocator under its
-// 256-register cap).  It addresses the env through the file-scope LDS object and rebuilds Consts from scalars: through
-// pointer arguments the LDS accesses would be compiled as flat loads.
-RV_DEV_NOINLINE void sim_run_fn(const rv_scene* scene, int stop_after, int n_arg, unsigned mask, float lin_thr, float ang_thr,
-                                int check_after, int min_stable, int max_steps) {
-  const Consts K = lds_consts(scene, stop_after);
-  sim_run_body(g_shared, K, run_req(n_arg, mask, lin_thr, ang_thr, check_after, min_stable, max_steps));
-}
-RV_DEV void sim_run(Shared& S, const Consts& K, const RunReq& rq) {
-  (void)S;
-  sim_run_fn(K.scene, K.stop_after, rq.n_arg, rq.mask, rq.lin_thr, rq.ang_thr, rq.check_after, rq.min_stable, rq.max_steps);
-}
-#else
+// (a forwarder on purpose: with the body under this name directly the compiler orders ~300 instructions of the awake substep
+// differently in both builds -- the same instructions.  Fold it once a benchmark of both builds shows the speed holds.)
 RV_DEV void sim_run(Shared& S, const Consts& K, const RunReq& rq) { sim_run_body(S, K, rq); }
-#endif
 
 // ------------------------------------------------- observation / reward --
 RV_DEV void compute_obs(DevEnv& e) {
@@ -5257,13 +5198,11 @@ struct ProgArgs {
   int k0, k_stop;
 };
 // returns (RV_PROG_PARTIAL) 1 when the env.step() completed in this launch
-// The segments of the env program as functions of their own (RV_SEGMENTS_NOINLINE: the two-waves-per-SIMD build).  Round 4
-// kept the substep LOOP out of line in that build and paid for it with the callee-saved registers of that one big function
-// (~100 KB of scratch per call: 49 - 130 GB of L2 write-outs per launch, profiles/r04_final_c{3,4,5}_pmc.txt).  Inverted in
-// round 5: the loop is inlined into the kernel (a kernel saves nothing) and what is called are the short straight-line
-// segments between two runs of it -- a callee only saves the callee-saved registers it uses itself.  Like sim_run_fn did,
-// a segment addresses the env through the file-scope LDS object and rebuilds Consts from scalars (through pointer
-// arguments the LDS accesses would be compiled as flat loads).
+// The segments of the env program as functions of their own (RV_SEGMENTS_NOINLINE: the two-waves-per-SIMD build).  Under
+// its 256-register cap the loop is inlined into the kernel (a kernel saves nothing) and what is called are the short
+// straight-line segments between two runs of it: a callee only saves the callee-saved registers it uses itself (the loop out
+// of line instead: 49 - 130 GB of L2 write-outs per launch, profiles/r04_final_c{3,4,5}_pmc.txt).  A segment addresses the env
+// through the file-scope LDS object and rebuilds Consts from scalars (see g_shared).
 #ifdef RV_SEGMENTS_NOINLINE
 #define RV_SEG_K const Consts K = lds_consts(scene, 0); Shared& S = g_shared;
 RV_DEV_NOINLINE void seg_step_prologue(const rv_scene* scene, int zero_counters, int count_step) { RV_SEG_K env_step_prologue(S, K, zero_counters, count_step); }

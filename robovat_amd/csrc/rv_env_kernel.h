@@ -15,6 +15,10 @@
 
 using namespace rv;
 
+#ifndef RV_ENV_OCCUPANCY_ATTR      // rv_kernels_occ2.hip sets it to its two-waves-per-SIMD attribute; no cap otherwise
+#define RV_ENV_OCCUPANCY_ATTR
+#endif
+
 // control words of the task queues (ints; every counter on a 128-byte line of its own)
 enum { RV_Q_NQ = 8, RV_Q_TAKEN = 0, RV_Q_ERR = 64, RV_Q_CTL_WORDS = 96 + 96 * RV_Q_NQ + 64 };
 // measurement words (RV_QUEUE_DEBUG): per XCD the tasks it ran, the envs it kept, when its last workgroup left (s_memtime >> 10)
@@ -69,12 +73,7 @@ struct EnvKernelArgs {
 template <int TMODE>
 __device__ __forceinline__ void rv_env_task(const EnvKernelArgs& args, const int MODE, const int env, Shared& S, const Consts& K, const int k0, const int k_stop);
 template <int TMODE>
-#ifdef RV_WAVES_PER_EU      // experiment: cap the registers so that RV_WAVES_PER_EU waves fit a SIMD (tools/flag_variants.sh)
-#define RV_ENV_OCC __attribute__((amdgpu_waves_per_eu(RV_WAVES_PER_EU, RV_WAVES_PER_EU)))
-#else
-#define RV_ENV_OCC
-#endif
-__global__ __launch_bounds__(RV_ENV_THREADS) RV_ENV_OCC void k_env(EnvKernelArgs args) {
+__global__ __launch_bounds__(RV_ENV_THREADS) RV_ENV_OCCUPANCY_ATTR void k_env(EnvKernelArgs args) {
   const int MODE = TMODE >= 0 ? TMODE : args.mode;
   Shared& S = g_shared;
   const bool queued = TMODE < 0 && args.q_slots != nullptr;      // (the run-time-dispatched instantiation only)
@@ -350,8 +349,7 @@ static inline void rv_launch_k_env_here(int mode, const EnvKernelArgs& a0, int n
   const dim3 g((unsigned)n_grid), b(64);
   EnvKernelArgs a = a0;
   a.mode = mode;
-  static const bool force_dispatch = getenv("RV_FORCE_DISPATCH") != nullptr;      // (measurement aid)
-  if (mode == MODE_ROLLOUT && a.q_slots == nullptr && !force_dispatch) hipLaunchKernelGGL(k_env<MODE_ROLLOUT>, g, b, 0, stream, a);
+  if (mode == MODE_ROLLOUT && a.q_slots == nullptr) hipLaunchKernelGGL(k_env<MODE_ROLLOUT>, g, b, 0, stream, a);
   else hipLaunchKernelGGL(k_env<-1>, g, b, 0, stream, a);
 }
 // workgroups of the run-time-dispatched kernel that are resident on one CU at a time (the queue's grid is this x CUs)

@@ -595,16 +595,14 @@ __global__ void k_queue_init(int* q, long long words) {
 // MODE_ROLLOUT of n_steps through the task queues?  Worlds with more envs than resident workgroups (RV_QUEUE=0: never)
 // pool > 0: the work-conserving rollout (rv_rollout_async) -- `pool` tasks in all, an env goes back to the tail after every
 // step, so the envs take turns and one in a slow state simply gets fewer of them
+// (`a` arrives with the queues off: launch_env)
 static int queue_setup(rv_world* w, int n_steps, EnvKernelArgs& a, long long pool = 0) {
-  a.q_slots = nullptr; a.q_ctl = nullptr; a.q_cap = 0; a.q_total = 0; a.q_pool = 0; a.q_launch = 0; a.q_wt = 0; a.q_sticky = 0; a.q_debug = 0; a.q_global = 0; a.q_steal = 0;
   const char* q = getenv("RV_QUEUE");      // (read per launch: the tests compare the two schedules in one process)
   // (measured with the per-XCD queues and the keep rule of k_env, profiles/r06_queue_variants.txt -- 8192 envs: 20 steps + 14 %, 10 steps
   // + 13 ... 16 %, 5 steps + 16 ... 19 %, 2 steps - 5 %; 4096 concave envs x 10 steps, bound by their slowest env: + - 0;
   // 8192 envs without deactivation, 8 steps, bound by envs that get slower step after step: - 6 %.  Rollouts of 10 steps and
-  // more go through the queues.  RV_QUEUE=1 forces them, 0 forbids them, RV_QUEUE_MIN_STEPS moves the threshold)
-  const char* qm = getenv("RV_QUEUE_MIN_STEPS");
-  const int min_steps = qm ? atoi(qm) : RV_QUEUE_MIN_STEPS;
-  if ((q && atoi(q) == 0) || w->q_grid <= 0 || w->n <= w->q_grid || (pool == 0 && n_steps < min_steps && !(q && atoi(q) == 1))) return RV_OK;
+  // more (RV_QUEUE_MIN_STEPS) go through the queues.  RV_QUEUE=1 forces them, 0 forbids them)
+  if ((q && atoi(q) == 0) || w->q_grid <= 0 || w->n <= w->q_grid || (pool == 0 && n_steps < RV_QUEUE_MIN_STEPS && !(q && atoi(q) == 1))) return RV_OK;
   const size_t total = pool > 0 ? (size_t)pool : (size_t)w->n * (size_t)n_steps;      // tasks that are begun
   if (total > ((size_t)1 << 24)) return RV_OK;      // (8 rings of `total` ints: 512 MB at most)
   // a ring holds what ONE XCD may be handed in the worst case: every task of the launch (an env is published once per
