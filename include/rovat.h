@@ -436,6 +436,34 @@ typedef struct rv_antipodal_params {
 int  rv_policy_antipodal(rv_world* w, const float* d_depth, const rv_antipodal_params* h_params, int32_t macro_index,
                          float* d_image_grasps, float* d_actions4, int32_t* d_status);
 
+/* ---- planning-mode PushReward: get_reward_fn(task, layout, is_planning=True) (push_reward.py:272-374 with the
+ *      planning branches :110-151 insertion_termination, :168-200 crossing_termination, :230-238 check_stride,
+ *      :241-254 check_border, :257-269 check_target_border, :312-357), what a sampling-based planner scores the
+ *      candidate transitions of its plans with.  States are the xy positions of B bodies, [..][B][2] float32; task,
+ *      tile lists, tile size and offset are the world's rv_config (task, region, goal, n_region, n_goal, tile_size,
+ *      tile_offset); RV_TASK_NONE gives reward 1, termination 0 (dummy_reward_fn, :34-47).  The semantics are written
+ *      out in csrc/rv_dev_plan.h.  Neither call reads more of an env than its last observation, and neither changes
+ *      any env state.  Asynchronous on the world's stream.  RV_ERR_VALUE: n_bodies outside 1..RV_MAXB, s < 1, h < 1,
+ *      m < 0, a missing required pointer, a buffer that is not 8-byte aligned, a grasp world. ---- */
+typedef struct rv_plan_params {
+  int32_t n_bodies;          /* B, 1..RV_MAXB: bodies per state (the reference uses state.shape[1]) */
+  int32_t is_high_level;     /* stride limits 0.1 / 0.3 instead of 0.01 / 0.15 (:313-322)           */
+  int32_t use_dense_reward, use_time_penalty;
+  float   goal_reward, termination_reward, dense_reward, time_reward;  /* 100, -100, 1, -1 (:274-277) */
+  float   gamma;             /* discount of rv_plan_score; 1 = plain sum                            */
+} rv_plan_params;
+/* reward_fn(state, next_state) for m independent transitions: d_state, d_next_state [m][B][2]; d_reward [m],
+ * d_termination [m] (1 = terminated or goal reached).  m = 0 is a no-op. */
+int  rv_plan_reward(rv_world* w, const rv_plan_params* h_params, const float* d_state, const float* d_next_state,
+                    int64_t m, float* d_reward /* [m] */, uint8_t* d_termination /* [m] */);
+/* s candidate plans of h steps for each of the N envs.  d_plans [N][s][h][B][2] are the states AFTER each step;
+ * d_state0 [N][B][2] is the state before the first one, NULL = the xy of the env's last observation.  Per plan, in
+ * float32: ret = 0, disc = 1, len = h; for t in 0..h-1: (r, term) = reward_fn(s_t, s_t+1); ret += disc * r; if term:
+ * len = t + 1, stop; disc *= gamma.  d_returns [N][s], d_lengths [N][s]; d_best [N]: the index of the largest return
+ * of the env, the lowest index among equals.  Any of the three may be NULL. */
+int  rv_plan_score(rv_world* w, const rv_plan_params* h_params, const float* d_state0, const float* d_plans,
+                   int32_t s, int32_t h, float* d_returns /* [N][s] */, int32_t* d_lengths /* [N][s] */, int32_t* d_best /* [N] */);
+
 /* ---- Simulator.step x n (simulator.py:94-103): ControllableBody.update +
  *      BulletPhysics.step (bullet_physics.py:106-109), no phase machine. ---- */
 int  rv_step_sub(rv_world* w, int32_t n_substeps);

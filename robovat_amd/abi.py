@@ -205,6 +205,14 @@ class rv_contact_query(C.Structure):
     _fields_ = [('body_a', i32), ('link_a', i32), ('body_b', i32), ('link_b', i32)]
 
 
+class rv_plan_params(C.Structure):
+    _fields_ = [
+        ('n_bodies', i32), ('is_high_level', i32), ('use_dense_reward', i32), ('use_time_penalty', i32),
+        ('goal_reward', f32), ('termination_reward', f32), ('dense_reward', f32), ('time_reward', f32),
+        ('gamma', f32),
+    ]
+
+
 def assign(arr, values):
     """Copy a (nested) python/numpy sequence into a ctypes array."""
     for i, v in enumerate(values):

@@ -5,6 +5,7 @@
 //   k_env<MODE>     one wave64 per env, the whole reset / macro step / n
 //                   substeps / settle loop out of LDS (rv_dev_env.h)
 //   k_contact_points one wave64 per env: the PyBullet contact records (rv_dev_contacts.h)
+//   k_plan_score    one workgroup per env, lanes over candidate plans: planning-mode PushReward (rv_dev_plan.h)
 //   k_*             small one-thread-per-env accessors behind the getters,
 //                   setters, observation, reward and policy entry points
 #include <hip/hip_runtime.h>
@@ -23,6 +24,7 @@
 #include "rv_dev_obs.h"
 #include "rv_dev_grasp_sampler.h"
 #include "rv_dev_contacts.h"
+#include "rv_dev_plan.h"
 
 using namespace rv;
 
@@ -692,6 +694,31 @@ static int launch_point_cloud(rv_world* w, size_t n_snaps, float* d_out) {
   return RV_OK;
 }
 
+// the checks rv_plan_reward and rv_plan_score share
+static int plan_check(const rv_world* w, const rv_plan_params* p, const char* who) {
+  if (!p) return fail(RV_ERR_VALUE, std::string(who) + ": null params");
+  if (w->cfg.env_type == RV_ENV_GRASP) return fail(RV_ERR_VALUE, std::string(who) + ": a PushEnv world only");
+  if (p->n_bodies < 1 || p->n_bodies > RV_MAXB) return fail(RV_ERR_VALUE, std::string(who) + ": n_bodies outside [1, RV_MAXB]");
+  return RV_OK;
+}
+static bool aligned_to(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
+// the kernel for B bodies; V4: the [4][2] records are read as two float4 (a 16-byte aligned base)
+#define PLAN_DISPATCH(B, V4, F, ...) do { \
+    switch (B) { \
+      case 1: F<1, false>(__VA_ARGS__); break; \
+      case 2: F<2, false>(__VA_ARGS__); break; \
+      case 3: F<3, false>(__VA_ARGS__); break; \
+      default: if (V4) F<4, true>(__VA_ARGS__); else F<4, false>(__VA_ARGS__); break; \
+    } } while (0)
+template <int B, bool V4>
+static void launch_plan_reward(rv_world* w, const rv_plan_params& p, const float* s, const float* nx, long long m, float* r, uint8_t* t) {
+  hipLaunchKernelGGL((k_plan_reward<B, V4>), dim3((unsigned)((m + 255) / 256)), dim3(256), 0, w->stream, w->d_cfg, p, s, nx, m, r, t);
+}
+template <int B, bool V4>
+static void launch_plan_score(rv_world* w, const PlanArgs& a, int tpb) {
+  hipLaunchKernelGGL((k_plan_score<B, V4>), dim3((unsigned)w->n), dim3((unsigned)tpb), 0, w->stream, w->d_envs, w->d_cfg, a);
+}
+
 extern "C" {
 
 const char* rv_last_error(void) { return g_err.c_str(); }
@@ -1075,6 +1102,38 @@ int rv_policy_antipodal(rv_world* w, const float* d_depth, const rv_antipodal_pa
   int rc = ensure_floats(w, &w->d_ap_scratch, &w->ap_scratch_cap, (size_t)w->n * 2 * a.Hc * a.Wc); if (rc != RV_OK) return rc;
   a.depth = d_depth; a.scratch = w->d_ap_scratch;
   hipLaunchKernelGGL(k_policy_antipodal, dim3((unsigned)w->n), dim3(RV_AP_TPB), 0, w->stream, w->d_envs, w->n, w->d_cfg, a);
+  HIPCHK(hipGetLastError());
+  return RV_OK;
+}
+int rv_plan_reward(rv_world* w, const rv_plan_params* h_params, const float* d_state, const float* d_next_state,
+                   int64_t m, float* d_reward, uint8_t* d_termination) {
+  WCHK(w);
+  int rc = plan_check(w, h_params, "rv_plan_reward"); if (rc != RV_OK) return rc;
+  if (m < 0) return fail(RV_ERR_VALUE, "rv_plan_reward: m must not be negative");
+  if (m == 0) return RV_OK;
+  NEED(d_state, "rv_plan_reward"); NEED(d_next_state, "rv_plan_reward"); NEED(d_reward, "rv_plan_reward"); NEED(d_termination, "rv_plan_reward");
+  if (!aligned_to(d_state, 8) || !aligned_to(d_next_state, 8)) return fail(RV_ERR_VALUE, "rv_plan_reward: the state buffers must be 8-byte aligned");
+  if ((m + 255) / 256 > 0x7fffffffLL) return fail(RV_ERR_VALUE, "rv_plan_reward: m too large for one launch");
+  const bool v4 = aligned_to(d_state, 16) && aligned_to(d_next_state, 16);
+  const rv_plan_params p = *h_params;
+  PLAN_DISPATCH(p.n_bodies, v4, launch_plan_reward, w, p, d_state, d_next_state, (long long)m, d_reward, d_termination);
+  HIPCHK(hipGetLastError());
+  return RV_OK;
+}
+int rv_plan_score(rv_world* w, const rv_plan_params* h_params, const float* d_state0, const float* d_plans,
+                  int32_t s, int32_t h, float* d_returns, int32_t* d_lengths, int32_t* d_best) {
+  WCHK(w);
+  int rc = plan_check(w, h_params, "rv_plan_score"); if (rc != RV_OK) return rc;
+  if (s < 1 || h < 1) return fail(RV_ERR_VALUE, "rv_plan_score: s and h must be positive");
+  NEED(d_plans, "rv_plan_score");
+  if (!aligned_to(d_plans, 8) || !aligned_to(d_state0, 8)) return fail(RV_ERR_VALUE, "rv_plan_score: the plan and state buffers must be 8-byte aligned");
+  PlanArgs a;
+  a.p = *h_params; a.state0 = d_state0; a.plans = d_plans; a.S = s; a.H = h;
+  a.returns = d_returns; a.lengths = d_lengths; a.best = d_best;
+  // one workgroup per env; as many waves as the env has plans for, 16 at the most (a lane then walks several plans)
+  const int tpb = s <= 64 ? 64 : (s <= 256 ? 256 : RV_PLAN_MAX_TPB);
+  const bool v4 = aligned_to(d_plans, 16);
+  PLAN_DISPATCH(a.p.n_bodies, v4, launch_plan_score, w, a, tpb);
   HIPCHK(hipGetLastError());
   return RV_OK;
 }

@@ -33,6 +33,7 @@ SYMBOLS = [
     'rv_rollout_record', 'rv_render', 'rv_set_gravity', 'rv_rollout_record_full', 'rv_step_begin', 'rv_step_poll', 'rv_set_constraint', 'rv_render_rgb', 'rv_set_friction', 'rv_set_auto_reset',
     'rv_set_constraint_ex', 'rv_set_link_path', 'rv_get_robot_ready', 'rv_get_camera', 'rv_set_max_joint_velocities',
     'rv_policy_antipodal', 'rv_get_contact_points', 'rv_env_kernel_build',
+    'rv_plan_reward', 'rv_plan_score',
 ]
 
 _EXC = {abi.RV_ERR_VALUE: ValueError, abi.RV_ERR_STATE: RuntimeError,
@@ -168,6 +169,8 @@ def load():
     lib.rv_get_camera.argtypes = [vp, vp]
     lib.rv_policy_antipodal.argtypes = [vp, vp, C.POINTER(abi.rv_antipodal_params), i32, vp, vp, vp]
     lib.rv_get_contact_points.argtypes = [vp, C.POINTER(abi.rv_contact_query), i32, vp, vp, vp]
+    lib.rv_plan_reward.argtypes = [vp, C.POINTER(abi.rv_plan_params), vp, vp, C.c_int64, vp, vp]
+    lib.rv_plan_score.argtypes = [vp, C.POINTER(abi.rv_plan_params), vp, vp, i32, i32, vp, vp, vp]
     for name in ('rv_set_actions', 'rv_get_body_state', 'rv_set_body_state',
                  'rv_get_body_params', 'rv_set_body_params', 'rv_get_joint_state',
                  'rv_set_joint_state', 'rv_get_link_poses', 'rv_get_env_counters',
@@ -216,6 +219,20 @@ def antipodal_params(config=None):
             phi = np.exp(-0.5 / (sigma * sigma) * x ** 2)
             phi /= phi.sum()
             abi.assign(p.gauss_weights, phi[radius:].astype(np.float32).tolist())
+    return p
+
+
+def plan_params(**overrides):
+    """The ``rv_plan_params`` of ``get_reward_fn(..., is_planning=True)`` with the reference's defaults
+    (push_reward.py:272-281): n_bodies 4, low level, goal 100, termination -100, dense 1, time -1, both terms on;
+    gamma 1 (``rv_plan_score`` sums the rewards).  Keyword arguments override fields."""
+    p = abi.rv_plan_params(n_bodies=abi.RV_MAXB, is_high_level=0, use_dense_reward=1, use_time_penalty=1,
+                           goal_reward=100.0, termination_reward=-100.0, dense_reward=1.0, time_reward=-1.0, gamma=1.0)
+    names = [n for n, _ in abi.rv_plan_params._fields_]
+    for k, v in overrides.items():
+        if k not in names:
+            raise TypeError('plan_params: unknown field %r' % (k,))
+        setattr(p, k, type(getattr(p, k))(v))
     return p
 
 
@@ -423,6 +440,53 @@ class World(object):
         check(self.lib.rv_policy_antipodal(self.h, None if d is None else self._ptr(d), C.byref(params), int(macro_index),
                                            self._ptr(g), None if a is None else self._ptr(a), self._ptr(st)))
         return g, a, st
+
+    def _plan_in(self, x, tail):
+        """float32, contiguous, on the device and 16-byte aligned (the kernels read a [4][2] record as two float4);
+        a trailing z column ([..., 3] positions) is dropped"""
+        t = self.torch.as_tensor(x, dtype=self.torch.float32, device=self.device)
+        if t.dim() >= 1 and t.shape[-1] == 3:
+            t = t[..., :2]
+        if tuple(t.shape[t.dim() - len(tail):]) != tuple(tail):
+            raise ValueError('expected [..., %s] positions, got %s' % (', '.join(str(v) for v in tail), tuple(t.shape)))
+        t = t.contiguous()
+        return t.clone() if t.data_ptr() % 16 else t
+
+    def plan_reward(self, state, next_state, params=None):
+        """rv_plan_reward: planning-mode PushReward of M transitions, ``state`` / ``next_state`` [M, B, 2] (or
+        [M, B, 3]; B from the tensor unless ``params`` is given).  Returns (reward float32 [M], termination uint8 [M])."""
+        s = self.torch.as_tensor(state)
+        if s.dim() != 3:
+            raise ValueError('plan_reward: state must be [M, B, 2]')
+        m, b = int(s.shape[0]), int(s.shape[1])
+        p = params if params is not None else plan_params(n_bodies=b)
+        s = self._plan_in(s, (b, 2)); nx = self._plan_in(next_state, (b, 2))
+        if tuple(nx.shape) != tuple(s.shape) or int(p.n_bodies) != b:
+            raise ValueError('plan_reward: state, next_state and params.n_bodies disagree')
+        r = self._new((m,), self.torch.float32)
+        t = self._new((m,), self.torch.uint8)
+        check(self.lib.rv_plan_reward(self.h, C.byref(p), self._ptr(s), self._ptr(nx), m, self._ptr(r), self._ptr(t)))
+        return r, t
+
+    def plan_score(self, plans, state0=None, params=None):
+        """rv_plan_score: ``plans`` [N, S, H, B, 2] (or [..., 3]) are the states after each step of S candidate plans
+        per env, ``state0`` [N, B, 2] the state before the first (None: the xy of the env's last observation).
+        Returns (returns float32 [N, S], lengths int32 [N, S], best int32 [N])."""
+        pl = self.torch.as_tensor(plans)
+        if pl.dim() != 5 or int(pl.shape[0]) != self.n:
+            raise ValueError('plan_score: plans must be [N, S, H, B, 2] with N = %d' % self.n)
+        s, h, b = int(pl.shape[1]), int(pl.shape[2]), int(pl.shape[3])
+        p = params if params is not None else plan_params(n_bodies=b)
+        if int(p.n_bodies) != b:
+            raise ValueError('plan_score: plans and params.n_bodies disagree')
+        pl = self._plan_in(pl, (b, 2))
+        s0 = None if state0 is None else self._plan_in(state0, (b, 2)).reshape(self.n, b, 2)
+        ret = self._new((self.n, s), self.torch.float32)
+        ln = self._new((self.n, s), self.torch.int32)
+        best = self._new((self.n,), self.torch.int32)
+        check(self.lib.rv_plan_score(self.h, C.byref(p), None if s0 is None else self._ptr(s0), self._ptr(pl), s, h,
+                                     self._ptr(ret), self._ptr(ln), self._ptr(best)))
+        return ret, ln, best
 
     # -- state
     def _get(self, fn, shape, dtype):

@@ -9,6 +9,12 @@ goldens includes the reference's quirks that downstream users see
 (SURVEY.md Appendix B-8): the clearing score's overwritten minimum, the
 all-False insertion termination outside planning mode, and tile centres that
 move with the ``size`` argument of ``check_on_tiles``.
+
+``is_planning=True`` is the transition check a sampling-based planner scores
+candidate plans with (``push_reward.py:110-151, 168-200, 230-269, 312-357``):
+stride limits, table border, target border and the two middle states of the
+straight line between the states; its termination penalty is not masked by
+the goal.  ``rv_plan_reward`` / ``rv_plan_score`` compute it on the device.
 """
 import numpy as np
 
@@ -70,6 +76,44 @@ def _termination(task, next_state, layout):
     return np.zeros(next_state.shape[0], dtype=bool)
 
 
+def _middle_states(state, next_state):
+    return state + (1. / 3.) * (next_state - state), state + (2. / 3.) * (next_state - state)
+
+
+def _planning_termination(task, state, next_state, layout):
+    """insertion_termination / crossing_termination with is_planning=True (push_reward.py:110-151, 168-200)."""
+    term = np.zeros(next_state.shape[0], dtype=bool)
+    if task == 'insertion':
+        size = layout.size * 1.25
+        for s in (next_state,) + _middle_states(state, next_state):
+            for i in range(next_state.shape[1]):
+                term |= check_on_tiles(s[:, i, :], layout.region, size, layout.offset)
+    elif task == 'crossing':
+        on_bridge = np.ones(next_state.shape[0], dtype=bool)
+        for s in (next_state,) + _middle_states(state, next_state):
+            on_bridge &= check_on_tiles(s[:, 0, :], layout.region, layout.size, layout.offset, max_dist=layout.size)
+        term = ~on_bridge
+    return term
+
+
+def check_stride(state, next_state, min_stride, max_stride):
+    strides = np.linalg.norm(next_state - state, axis=-1)
+    return np.all(strides < min_stride, axis=1) | np.any(strides > max_stride, axis=1)
+
+
+def _outside(x, y, x_range, y_range, tolerance):
+    return ((x < x_range[0] - tolerance) | (x > x_range[1] + tolerance) |
+            (y < y_range[0] - tolerance) | (y > y_range[1] + tolerance))
+
+
+def check_border(state, next_state, x_range=(0.22, 0.98), y_range=(-0.56, 0.66), tolerance=0.02):
+    return np.any(_outside(next_state[..., 0], next_state[..., 1], x_range, y_range, tolerance), axis=1)
+
+
+def check_target_border(state, next_state, x_range=(0.3, 0.8), y_range=(-0.56, 0.66), tolerance=0.02):
+    return _outside(next_state[:, 0, 0], next_state[:, 0, 1], x_range, y_range, tolerance)
+
+
 def dummy_reward_fn(state, next_state):
     state = process_state(state)
     shape = () if state.ndim == 2 else (state.shape[0],)
@@ -83,9 +127,32 @@ def get_reward_fn(task_name, layout_id, goal_reward=100.0, termination_reward=-1
         return dummy_reward_fn
     if task_name not in push_layouts.TASK_NAME_TO_LAYOUTS:
         raise ValueError('Unrecognized manipulation task: %r' % task_name)
-    if is_planning:
-        raise NotImplementedError('planning-mode checks are outside the env.step() path')
     layout = push_layouts.TASK_NAME_TO_LAYOUTS[task_name][layout_id]
+
+    def planning_reward_fn(state, next_state):
+        state, next_state = process_state(state), process_state(next_state)
+        if is_high_level:
+            termination = check_stride(state, next_state, min_stride=0.1, max_stride=0.3)
+        else:
+            termination = check_stride(state, next_state, min_stride=0.01, max_stride=0.15)
+        termination = termination | check_border(state, next_state)
+        if task_name == 'insertion':
+            termination = termination | check_target_border(state, next_state)
+        termination = termination | _planning_termination(task_name, state, next_state, layout)
+        goal = _goal(task_name, next_state, layout) & ~termination
+        # (the float32 accumulator and the order of its updates are the reference's, :309-370; the penalty
+        # is not masked by the goal in planning mode, :351-357)
+        reward = np.zeros(state.shape[0], dtype=np.float32)
+        reward += goal_reward * goal.astype(np.float32)
+        reward += termination_reward * termination.astype(np.float32)
+        if use_dense_reward:
+            reward += np.abs(_score(task_name, next_state, layout) - _score(task_name, state, layout)) * dense_reward
+        if use_time_penalty:
+            reward += time_reward
+        return reward, termination | goal
+
+    if is_planning:
+        return planning_reward_fn
 
     def reward_fn(state, next_state):
         state, next_state = process_state(state), process_state(next_state)
