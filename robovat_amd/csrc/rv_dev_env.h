@@ -333,11 +333,12 @@ struct LimbFK {
   v3 axis[RV_NLIMB];
 };
 // local joint rotation jquat_i o Rz(q_i)
-RV_DEV q4 joint_local_quat(const rv_arm* a, int i, float qi) {
+RV_DEV q4 joint_local_quat_of(q4 jquat, float qi) {      // (jquat_i already in registers)
   float s, c; sincosr(qi * 0.5f, &s, &c);
   q4 qz; qz.x = 0.0f; qz.y = 0.0f; qz.z = s; qz.w = c;
-  return qmul(ldq(a->jquat[i]), qz);
+  return qmul(jquat, qz);
 }
+RV_DEV q4 joint_local_quat(const rv_arm* a, int i, float qi) { return joint_local_quat_of(ldq(a->jquat[i]), qi); }
 // chain composition given the local joint quaternions lq[0..6]
 RV_DEV void fk_chain(const rv_arm* a, const q4* lq, LimbFK& F) {
   v3 pp = ld3(a->base_pos);
@@ -801,13 +802,19 @@ RV_DEV void refresh_point(const Shared& S, const Consts& K, int kind, int a, int
   *dist = d; *rm = r;
 }
 // store the refreshed distances, drop the broken points (highest slot first); returns how many were lost
-RV_DEV int refresh_apply(DevMan& m, const float* dist, const int* rm) {
-  const int n0 = m.n;
+// (n0: the manifold's point count, dist / rm: the refresh results, all loaded by the caller ahead of its first store; the
+// count is carried in a register from there on.  A removal itself -- rare -- still moves the last point through memory.)
+RV_DEV int refresh_apply(DevMan& m, const int n0, const float* dist, const int* rm) {
+  int n = n0;
 #pragma unroll
   for (int i = 0; i < 4; ++i) if (i < n0) m.dist[i] = dist[i];
 #pragma unroll
-  for (int i = 3; i >= 0; --i) if (i < n0 && rm[i]) man_remove(m, i);
-  return n0 - m.n;
+  for (int i = 3; i >= 0; --i) if (i < n0 && rm[i]) {
+    const int last = n - 1;
+    if (i != last) { ManPoint p = man_get(m, last); man_put(m, i, p); }
+    n = last; m.n = last;
+  }
+  return n0 - n;
 }
 RV_DEV void manifold_add_world(const Shared& S, const Consts& K, int kind, int a, int b, int col, DevMan& m, v3 wa, v3 wb, v3 n, float d, float brk) {
   v3 la = to_local_body(S, a, wa), lb;
@@ -2401,6 +2408,7 @@ RV_DEV void arm_motor_phases(Shared& S, const Consts& K, const int with_lq, cons
   // line in joint space.
   RV_LANES_BEGIN
     if (lane < RV_NJ) {
+      // (loads first, stores last: DESIGN.md §10, "LDS staging")
       DevEnv& e = S.e; int j = lane; float dt = c->dt;
       float sync = 1.0f;
 #if RV_ON_DEVICE
@@ -2409,30 +2417,43 @@ RV_DEV void arm_motor_phases(Shared& S, const Consts& K, const int with_lq, cons
 #pragma unroll
       for (int k = 0; k < RV_NLIMB; ++k) sync = fminr(sync, S.s.ratio[k]);
 #endif
+      const int motor_on = e.motor_on[j], limb_dyn = c->limb_dynamics;
+      const float vdraw = S.s.vdraw[j], vmax = e.vmax_cmd[j], qd0 = e.qd[j], q0 = e.q[j];
+      const float a_max = arm->a_max[j], q_lo = arm->q_lo[j], q_hi = arm->q_hi[j];
+      const int jq = j < RV_NLIMB ? j : 0;      // (the joint quaternion of a limb joint: index clamped for the fingers)
+      const q4 jquat = ldq(arm->jquat[jq]);
+      float travel = 0.0f; int steps0 = 0, steps1 = 0;
+      if (count_step == 1) { travel = S.s.jtravel[j]; steps0 = e.sim_steps; steps1 = e.substeps_last; }
+      if (count_step == 2) travel = S.s.ftravel[j];
+      // ---- arithmetic on the locals
       float vd = 0.0f;
-      if (e.motor_on[j]) {
-        vd = S.s.vdraw[j];
+      if (motor_on) {
+        vd = vdraw;
         if (j < RV_NLIMB) vd = vd * sync;
-        vd = fclamp_pm(vd, e.vmax_cmd[j]);
+        vd = fclamp_pm(vd, vmax);
       }
-      float dv = fclamp_pm(vd - e.qd[j], arm->a_max[j] * dt);
-      float qd = e.qd[j] + dv;
-      float qn = e.q[j] + qd * dt;
-      if (qn < arm->q_lo[j]) { qn = arm->q_lo[j]; qd = 0.0f; }
-      if (qn > arm->q_hi[j]) { qn = arm->q_hi[j]; qd = 0.0f; }
+      float dv = fclamp_pm(vd - qd0, a_max * dt);
+      float qd = qd0 + dv;
+      float qn = q0 + qd * dt;
+      if (qn < q_lo) { qn = q_lo; qd = 0.0f; }
+      if (qn > q_hi) { qn = q_hi; qd = 0.0f; }
+      q4 lq = jquat;
+      if (with_lq && j < RV_NLIMB) lq = joint_local_quat_of(jquat, qn);
+      travel += fabsr(qd) * dt;
+      // ---- stores
       if (j >= RV_NLIMB) { S.s.fing_dv[j - RV_NLIMB] = dv; S.s.fing_vt[j - RV_NLIMB] = vd; S.s.fing_qd0[j - RV_NLIMB] = qd; }
-      else if (c->limb_dynamics) { S.s.limb_dv[j] = dv; S.s.limb_vt[j] = vd; S.s.limb_qd0[j] = qd; }
-      if (with_lq) S.s.jchg[j] = (qn != e.q[j]) || (qd != 0.0f);   // did the joint state change at all?
+      else if (limb_dyn) { S.s.limb_dv[j] = dv; S.s.limb_vt[j] = vd; S.s.limb_qd0[j] = qd; }
+      if (with_lq) S.s.jchg[j] = (qn != q0) || (qd != 0.0f);   // did the joint state change at all?
       e.q[j] = qn; e.qd[j] = qd;
       if (with_lq) {
         S.s.jmoving[j] = fabsr(qd) > 1e-3f;
-        if (j < RV_NLIMB) stq(S.s.lq[j], joint_local_quat(arm, j, qn));
+        if (j < RV_NLIMB) stq(S.s.lq[j], lq);
       }
       if (count_step == 1) {
-        S.s.jtravel[j] += fabsr(qd) * dt;      // coasting: path length of the joint
-        if (j == 0) { e.sim_steps++; e.substeps_last++; }
+        S.s.jtravel[j] = travel;      // coasting: path length of the joint
+        if (j == 0) { e.sim_steps = steps0 + 1; e.substeps_last = steps1 + 1; }
       }
-      if (count_step == 2) S.s.ftravel[j] += fabsr(qd) * dt;   // an "arm far" substep: the boxes are not recomputed
+      if (count_step == 2) S.s.ftravel[j] = travel;   // an "arm far" substep: the boxes are not recomputed
     }
   RV_LANES_END
 }
@@ -2441,8 +2462,12 @@ RV_DEV void arm_lq_phase(Shared& S, const Consts& K) {
   RV_LANES_BEGIN
     if (lane < RV_NJ) {
       const DevEnv& e = S.e; int j = lane;
-      S.s.jmoving[j] = fabsr(e.qd[j]) > 1e-3f;
-      if (j < RV_NLIMB) stq(S.s.lq[j], joint_local_quat(K.arm, j, e.q[j]));
+      const float qd = e.qd[j], q = e.q[j];
+      const q4 jquat = ldq(K.arm->jquat[j < RV_NLIMB ? j : 0]);
+      q4 lq = jquat;
+      if (j < RV_NLIMB) lq = joint_local_quat_of(jquat, q);
+      S.s.jmoving[j] = fabsr(qd) > 1e-3f;
+      if (j < RV_NLIMB) stq(S.s.lq[j], lq);
     }
   RV_LANES_END
 }
@@ -2454,9 +2479,15 @@ RV_DEV void arm_fk_phases(Shared& S, const Consts& K) {
     if (lane == 0) {
       DevEnv& e = S.e;
       q4 pq = ldq(arm->base_quat);
+      const q4 j7 = ldq(arm->jquat[7]);
+      q4 lq[RV_NLIMB], fq[RV_NLIMB + 1];
 #pragma unroll
-      for (int i = 0; i < RV_NLIMB; ++i) { pq = qmul(pq, ldq(S.s.lq[i])); stq(e.fquat[i], pq); }
-      stq(e.fquat[7], qmul(pq, ldq(arm->jquat[7])));
+      for (int i = 0; i < RV_NLIMB; ++i) lq[i] = ldq(S.s.lq[i]);
+#pragma unroll
+      for (int i = 0; i < RV_NLIMB; ++i) { pq = qmul(pq, lq[i]); fq[i] = pq; }
+      fq[7] = qmul(pq, j7);
+#pragma unroll
+      for (int i = 0; i <= RV_NLIMB; ++i) stq(e.fquat[i], fq[i]);
     } else if (lane == 1) {
       int mv = 0;
 #pragma unroll
@@ -2469,14 +2500,19 @@ RV_DEV void arm_fk_phases(Shared& S, const Consts& K) {
     DevEnv& e = S.e;
     if (lane <= RV_NLIMB) {
       int i = lane;
-      q4 par = ldq(i == 0 ? arm->base_quat : e.fquat[i == 0 ? 0 : i - 1]);
-      st3(S.s.rvec[i], qrotv(par, ld3(arm->jpos[i])));
-      q4 qi = ldq(e.fquat[i]);
-      if (i < RV_NLIMB) st3(S.s.axis[i], qaxis_z(qi));
-      stm(S.s.frot[i], qmat(qi));
+      const q4 par = ldq(i == 0 ? arm->base_quat : e.fquat[i == 0 ? 0 : i - 1]);
+      const v3 jp = ld3(arm->jpos[i]);
+      const q4 qi = ldq(e.fquat[i]);
+      const v3 rv = qrotv(par, jp);
+      const v3 ax = qaxis_z(qi);
+      const m3 Rm = qmat(qi);
+      st3(S.s.rvec[i], rv);
+      if (i < RV_NLIMB) st3(S.s.axis[i], ax);
+      stm(S.s.frot[i], Rm);
     } else if (lane == 8 || lane == 9) {
-      q4 q7 = ldq(e.fquat[7]);
-      stm(S.s.frot[lane], qmat(q7));
+      const q4 q7 = ldq(e.fquat[7]);
+      const m3 R7 = qmat(q7);
+      stm(S.s.frot[lane], R7);
       stq(e.fquat[lane], q7);
     }
   RV_LANES_END
@@ -2487,12 +2523,16 @@ RV_DEV void arm_fk_phases(Shared& S, const Consts& K) {
       DevEnv& e = S.e;
       const int n = lane < 8 ? lane : 7;
       v3 p = ld3(arm->base_pos);
+      v3 rv[8];
 #pragma unroll
-      for (int k = 0; k < 8; ++k) if (k <= n) p = add(p, ld3(S.s.rvec[k]));
+      for (int k = 0; k < 8; ++k) rv[k] = ld3(S.s.rvec[k]);
+      const v3 yax = mk(S.s.frot[7][1], S.s.frot[7][4], S.s.frot[7][7]);
+      const int kf = lane >= 8 ? lane - 8 : 0;      // (finger index, clamped for the limb frames)
+      const float y0 = arm->finger_y0[kf], qf = e.q[7 + kf];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) if (k <= n) p = add(p, rv[k]);
       if (lane >= 8) {
-        int k = lane - 8;
-        v3 yax = mk(S.s.frot[7][1], S.s.frot[7][4], S.s.frot[7][7]);
-        float off = arm->finger_y0[k] + e.q[7 + k];
+        float off = y0 + qf;
         p = madd(p, yax, off);
       }
       st3(e.fpos[lane], p);
@@ -2505,61 +2545,108 @@ RV_DEV void arm_fk_phases(Shared& S, const Consts& K) {
 RV_DEV void arm_collider_phases(Shared& S, const Consts& K, const int arm_on) {
   const rv_config* c = K.cfg;
   const rv_arm* arm = K.arm;
+  // (loads first, stores last -- DESIGN.md §10, "LDS staging": a store into the Shared object between two of its loads
+  // cannot be proven disjoint from the later one, which then waits for its own round trip)
   RV_LANES_BEGIN
+    if (arm_on && lane < RV_NCOL) {
+      const int col = lane; const int f = arm->col_frame[col];
+      const v3 cc = ld3(arm->col_center[col]), hh = ld3(arm->col_half[col]);
+      const float margin = c->margin, dt = c->dt, cqd = c->contact_query_dist, tthick = c->table_thickness;
+      const float tcx = c->table_center[0], tcy = c->table_center[1], thx = c->table_half[0], thy = c->table_half[1];
+      const float brk = brk_col(arm, c, col);
+      const float table_z = S.e.table_z;
+      float reach = S.s.colext[col];
+      float qda[RV_NJ], jl[RV_NLIMB + 1];
+#pragma unroll
+      for (int j = 0; j < RV_NJ; ++j) qda[j] = S.e.qd[j];
+#pragma unroll
+      for (int j = 0; j <= RV_NLIMB; ++j) jl[j] = S.s.jlen[j];
+      float R[9];
+#pragma unroll
+      for (int k = 0; k < 9; ++k) R[k] = S.s.frot[f][k];
+      const v3 fp = ld3(S.e.fpos[f]);
+      // ---- arithmetic on the locals
+      const v3 cw = add(fp, mulv(R, cc));
+      const float colr = fsqrtr(hh.x * hh.x + hh.y * hh.y + hh.z * hh.z) + margin;
+      const float cwa[3] = {cw.x, cw.y, cw.z};
+      float lo[3], hi[3];
+#pragma unroll
+      for (int x = 0; x < 3; ++x) {
+        const float ext = fabsr(R[3 * x]) * hh.x + fabsr(R[3 * x + 1]) * hh.y + fabsr(R[3 * x + 2]) * hh.z;
+        lo[x] = cwa[x] - ext; hi[x] = cwa[x] + ext;
+      }
+      const float lo_z = lo[2];
+      // can the box be within the contact-query distance of the table?  (the two rejection tests of the
+      // arm-table detector)
+      v3 tc = mk(tcx, tcy, table_z - 0.5f * tthick);
+      v3 th = mk(thx, thy, 0.5f * tthick);
+      float r = colr + brk;
+      const int atflag = (!(lo_z - table_z - margin >= cqd) && sphere_box_dist2(cw, tc, th) < r * r) ? 1 : 0;
+      // how far a vertex of this box can have moved in this substep (joint travel x reach)
+      const int fl = f < 7 ? f : 7;
+      float tr = 0.0f;
+#pragma unroll
+      for (int j = RV_NLIMB; j >= 0; --j) {
+        if (j <= fl) {
+          if (j < RV_NLIMB) tr += reach * (fabsr(qda[j]) * dt);
+          reach += jl[j];
+        }
+      }
+      if (f >= 8) tr += fabsr(f == 8 ? qda[7] : qda[8]) * dt;
+      // ---- stores
+      st3(S.s.colc[col], cw);
+      S.s.colr[col] = colr;
+      S.s.colflag[col] = 0;
+#pragma unroll
+      for (int x = 0; x < 3; ++x) { S.s.colmin[col][x] = lo[x]; S.s.colmax[col][x] = hi[x]; }
+      S.s.atflag[col] = atflag;
+      S.s.coltravel[col] = tr * 1.02f + 1e-7f;
+    }
     if (lane >= 16 && lane < 16 + RV_MAXB) { S.s.wake[lane - 16] = 0; S.s.bnear[lane - 16] = 0; }
     if (lane == 24) S.s.near_any = 0;
     // (no arm in this substep -- the bodies settling after a reset: the boxes do not travel.  The wake test reads the travel
     // whatever arm_on is and keeps its distance bounds; in a launch that BEGINS with a reset nothing had written it yet, and a
     // negative left-over in LDS turned the bounds into "far away for ever" -- found by the poisoned-LDS build, round 5)
     if (!arm_on && lane < RV_NCOL) S.s.coltravel[lane] = 0.0f;
-    if (arm_on && lane < RV_NCOL) {
-      const int col = lane; const int f = arm->col_frame[col];
-      const v3 cc = ld3(arm->col_center[col]), hh = ld3(arm->col_half[col]);
-      const float* R = S.s.frot[f];
-      const v3 cw = add(ld3(S.e.fpos[f]), mulv(R, cc));
-      st3(S.s.colc[col], cw);
-      const float colr = fsqrtr(hh.x * hh.x + hh.y * hh.y + hh.z * hh.z) + c->margin;
-      S.s.colr[col] = colr;
-      S.s.colflag[col] = 0;
-      const float cwa[3] = {cw.x, cw.y, cw.z};
-      float lo_z = 0.0f;
-#pragma unroll
-      for (int x = 0; x < 3; ++x) {
-        const float ext = fabsr(R[3 * x]) * hh.x + fabsr(R[3 * x + 1]) * hh.y + fabsr(R[3 * x + 2]) * hh.z;
-        const float lo = cwa[x] - ext;
-        S.s.colmin[col][x] = lo; S.s.colmax[col][x] = cwa[x] + ext;
-        if (x == 2) lo_z = lo;
-      }
-      // can the box be within the contact-query distance of the table?  (the two rejection tests of the
-      // arm-table detector)
-      v3 tc = mk(c->table_center[0], c->table_center[1], S.e.table_z - 0.5f * c->table_thickness);
-      v3 th = mk(c->table_half[0], c->table_half[1], 0.5f * c->table_thickness);
-      float r = colr + brk_col(arm, c, col);
-      S.s.atflag[col] = (!(lo_z - S.e.table_z - c->margin >= c->contact_query_dist) &&
-                         sphere_box_dist2(cw, tc, th) < r * r) ? 1 : 0;
-      // how far a vertex of this box can have moved in this substep (joint travel x reach)
-      {
-        const DevEnv& e = S.e; const int fl = f < 7 ? f : 7;
-        float tr = 0.0f, reach = S.s.colext[col];
-        for (int j = fl; j >= 0; --j) {
-          if (j < RV_NLIMB) tr += reach * (fabsr(e.qd[j]) * c->dt);
-          reach += S.s.jlen[j];
-        }
-        if (f >= 8) tr += fabsr(e.qd[f - 1]) * c->dt;
-        S.s.coltravel[col] = tr * 1.02f + 1e-7f;
-      }
-    }
     if (lane == 63) { S.s.kin_fresh = arm_on; S.s.clr_valid = 0; S.s.far_valid = arm_on; }   // left-over clearances are for coasting chains only
     if (lane >= 32 && lane < 32 + RV_NJ) S.s.ftravel[lane - 32] = 0.0f;
   RV_LANES_END
 }
 // the eight world vertices of collider box col (lane k < 8 of the caller's choice)
-RV_DEV void arm_box_vertex(Shared& S, const Consts& K, const int col, const int k) {
+RV_DEV v3 arm_box_vertex_world(const Shared& S, const Consts& K, const int col, const int k) {
   const rv_arm* arm = K.arm;
   const int f = arm->col_frame[col];
   const v3 cc = ld3(arm->col_center[col]), hh = ld3(arm->col_half[col]);
   const v3 l = mk(cc.x + ((k & 1) ? hh.x : -hh.x), cc.y + ((k & 2) ? hh.y : -hh.y), cc.z + ((k & 4) ? hh.z : -hh.z));
-  st3(S.s.colv[col][k], add(ld3(S.e.fpos[f]), mulv(S.s.frot[f], l)));
+  return add(ld3(S.e.fpos[f]), mulv(S.s.frot[f], l));
+}
+// One lane's share of the vertex phases (the wake test's stage 2a, the narrow-phase preparation), loads first and stores
+// last ("LDS staging").  A lane holds vertex (lane & 7) of collider box (lane >> 3) and, for lanes
+// below 16, of box 8 + (lane >> 3); and vertex (lane % RV_MAXV) of hull (lane / RV_MAXV) of EVERY body.  The hull
+// vertices come from global memory: the four loads of a lane are issued together, ahead of every LDS store, with
+// the indices of a vertex that is not wanted clamped to vertex 0 of shape 0.
+static_assert(RV_MAXH * RV_MAXV == 64 && RV_NCOL * 8 <= 128, "vertex phases: one hull vertex per body and two box vertices per lane");
+struct VertexLoads { v3 hl[RV_MAXB]; int hok[RV_MAXB]; v3 bv[2]; int bok[2]; };
+RV_DEV void hull_vertex_load(const Shared& S, const Consts& K, const int lane, const int b, const int need, VertexLoads& V) {
+  const int h = lane / RV_MAXV, i = lane % RV_MAXV;
+  const int ok = (need != 0) & (h < S.n_hulls[b]) & (i < S.n_verts[b][h]);
+  const rv_shape* s = &K.scene->shapes[ok ? S.e.shape[b] : 0];
+  const float sc = S.e.scale[b];
+  const float* v = s->verts[ok ? h : 0][ok ? i : 0];
+  V.hl[b] = mk(v[0] * sc, v[1] * sc, v[2] * sc);
+  V.hok[b] = ok;
+}
+RV_DEV void box_vertex_load(const Shared& S, const Consts& K, const int lane, const int t, const int need, VertexLoads& V) {
+  const int item = lane + 64 * t;
+  V.bok[t] = need; V.bv[t] = mk(0, 0, 0);
+  if (need) V.bv[t] = arm_box_vertex_world(S, K, item >> 3, item & 7);
+}
+RV_DEV void vertex_stores(Shared& S, const int lane, const VertexLoads& V, const v3* bpos, const m3* brot) {
+#pragma unroll
+  for (int t = 0; t < 2; ++t) if (V.bok[t]) st3(S.s.colv[(lane + 64 * t) >> 3][lane & 7], V.bv[t]);
+#pragma unroll
+  for (int b = 0; b < RV_MAXB; ++b)
+    if (V.hok[b]) st3(S.s.u.r.wv[b][lane / RV_MAXV][lane % RV_MAXV], add(bpos[b], mulv(brot[b], V.hl[b])));
 }
 
 #ifdef RV_EMU_COUNT
@@ -2575,37 +2662,65 @@ static long rv_emu_coasted = 0;
 // clearances of collider box col on fresh kinematics: how far the box is from the contact range
 // of the table and of the nearest body
 RV_DEV void coast_measure_clearances(Shared& S, const Consts& K, const int col) {
-  const rv_config* c = K.cfg; const DevEnv& e = S.e;
-  v3 tc = mk(c->table_center[0], c->table_center[1], e.table_z - 0.5f * c->table_thickness);
-  v3 th = mk(c->table_half[0], c->table_half[1], 0.5f * c->table_thickness);
-  const float zc = S.s.colmin[col][2] - e.table_z - c->margin - c->contact_query_dist;
-  const float sc = fsqrtr(sphere_box_dist2(ld3(S.s.colc[col]), tc, th)) - (S.s.colr[col] + brk_col(K.arm, c, col));
+  const rv_config* c = K.cfg; const DevEnv& e = S.e; const rv_arm* arm = K.arm;
+  // (loads first, stores last: DESIGN.md §10, "LDS staging")
+  const int f = arm->col_frame[col];
+  const float tcx = c->table_center[0], tcy = c->table_center[1], thx = c->table_half[0], thy = c->table_half[1];
+  const float tthick = c->table_thickness, margin = c->margin, cqd = c->contact_query_dist, wake_gap = c->wake_gap, breaking = c->breaking;
+  const float table_z = e.table_z;
+  const float cmin[3] = {S.s.colmin[col][0], S.s.colmin[col][1], S.s.colmin[col][2]};
+  const float cmax[3] = {S.s.colmax[col][0], S.s.colmax[col][1], S.s.colmax[col][2]};
+  const v3 cc = ld3(S.s.colc[col]);
+  const float colr = S.s.colr[col];
+  const float brkc = brk_col(arm, c, col);
+  int use[RV_MAXB]; float bb[RV_MAXB][6], rad[RV_MAXB], sep[RV_MAXB];
+#pragma unroll
+  for (int b = 0; b < RV_MAXB; ++b) {
+    use[b] = body_present(e, b) && !body_static(e, b);      // (the arm does not wake a static body)
+#pragma unroll
+    for (int k = 0; k < 6; ++k) bb[b][k] = e.baabb[b][k];
+    rad[b] = e.radius[b]; sep[b] = S.s.sep[b][col];
+  }
+  float cco[RV_NJ]; v3 fp[RV_NLIMB];
+#pragma unroll
+  for (int j = 0; j < RV_NJ; ++j) cco[j] = S.s.ccoef[col][j];
+#pragma unroll
+  for (int j = 0; j < RV_NLIMB; ++j) fp[j] = ld3(e.fpos[j]);
+  // ---- arithmetic on the locals
+  v3 tc = mk(tcx, tcy, table_z - 0.5f * tthick);
+  v3 th = mk(thx, thy, 0.5f * tthick);
+  const float zc = cmin[2] - table_z - margin - cqd;
+  const float sc = fsqrtr(sphere_box_dist2(cc, tc, th)) - (colr + brkc);
   const float tclear = zc > sc ? zc : sc;                 // either test rejecting is enough
   float bclear = 1e30f;
+#pragma unroll
   for (int b = 0; b < RV_MAXB; ++b) {
-    if (!body_present(e, b) || body_static(e, b)) continue;      // (the arm does not wake a static body)
-    float d = fsqrtr(aabb_aabb_dist2(e.baabb[b], e.baabb[b] + 3, S.s.colmin[col], S.s.colmax[col])) - (wake_range(e, K.arm, c, b, col) + 2.0f * c->margin);
-    d = fmaxr(d, S.s.sep[b][col]);   // the distance bound left by the last wake query, if better
+    if (!use[b]) continue;
+    // (wake_range: the smaller breaking threshold of the body and the box, capped by the wake gap)
+    const float wr = fminr(fminr(breaking * (rad[b] - margin), brkc), wake_gap);
+    float d = fsqrtr(aabb_aabb_dist2(bb[b], bb[b] + 3, cmin, cmax)) - (wr + 2.0f * margin);
+    d = fmaxr(d, sep[b]);   // the distance bound left by the last wake query, if better
     bclear = fminr(bclear, d);
   }
-  S.s.clr_t[col] = tclear; S.s.clr_b[col] = bclear;
   // Levers for the travel bound of the fused loop.  ccoef (the length of the chain from the joint
   // to the box, valid in any configuration) is what a folded arm never reaches: the distance R_j
   // from joint j's origin to the farthest point of the box, measured now, changes only through the
   // joints between j and the box, i.e. by no more than the box itself travels -- and the loop never
   // lets that exceed the clearance measured here.  So R_j + clearance bounds the lever for as long
   // as these clearances are in use.
-  {
-    const rv_arm* arm = K.arm;
-    const int f = arm->col_frame[col]; const int fl = f < RV_NLIMB ? f : RV_NLIMB - 1;
-    const float slack = fmaxr(fminr(tclear, 0.5f * bclear), 0.0f);
-    const v3 cc = ld3(S.s.colc[col]);
-    for (int j = 0; j < RV_NJ; ++j) {
-      float L = S.s.ccoef[col][j];
-      if (j <= fl && j < RV_NLIMB) L = fminr(L, (len(sub(cc, ld3(e.fpos[j]))) + S.s.colr[col] + slack) * 1.001f);
-      S.s.crun[col][j] = L;
-    }
+  const int fl = f < RV_NLIMB ? f : RV_NLIMB - 1;
+  const float slack = fmaxr(fminr(tclear, 0.5f * bclear), 0.0f);
+  float crun[RV_NJ];
+#pragma unroll
+  for (int j = 0; j < RV_NJ; ++j) {
+    float L = cco[j];
+    if (j < RV_NLIMB) { if (j <= fl) L = fminr(L, (len(sub(cc, fp[j < RV_NLIMB ? j : 0])) + colr + slack) * 1.001f); }
+    crun[j] = L;
   }
+  // ---- stores
+  S.s.clr_t[col] = tclear; S.s.clr_b[col] = bclear;
+#pragma unroll
+  for (int j = 0; j < RV_NJ; ++j) S.s.crun[col][j] = crun[j];
 }
 RV_DEV int coast_budget(Shared& S, const Consts& K, const int remaining, int* kidx) {
   const rv_config* c = K.cfg;
@@ -3188,19 +3303,28 @@ RV_DEV void arm_twist_lane(Shared& S, const Consts& K, const int f) {
   const rv_config* c = K.cfg;
   const DevEnv& e = S.e;
   const int kmax = f < RV_NLIMB ? f : RV_NLIMB - 1;
-  v3 pf = ld3(e.fpos[f]);
+  // (loads first, stores last: DESIGN.md §10, "LDS staging")
+  const v3 pf = ld3(e.fpos[f]);
+  v3 ax[RV_NLIMB], pk[RV_NLIMB]; float qdk[RV_NLIMB];
+#pragma unroll
+  for (int k = 0; k < RV_NLIMB; ++k) { ax[k] = ld3(S.s.axis[k]); qdk[k] = e.qd[k]; pk[k] = ld3(e.fpos[k]); }
+  const v3 yax = mk(S.s.frot[7][1], S.s.frot[7][4], S.s.frot[7][7]);
+  const float qdf = e.qd[f >= 8 ? f - 1 : RV_NLIMB];      // (finger slide velocity; index clamped for the limb frames)
+  const int fdyn = c->finger_dynamics;
+  const float fext = S.s.fext[f], dt = c->dt;
   v3 fw = mk(0, 0, 0), fv = mk(0, 0, 0);
 #pragma unroll
   for (int k = 0; k < RV_NLIMB; ++k) if (k <= kmax) {
-    v3 u = scale(ld3(S.s.axis[k]), e.qd[k]);
+    v3 u = scale(ax[k], qdk[k]);
     fw = add(fw, u);
-    fv = add(fv, cross(u, sub(pf, ld3(e.fpos[k]))));
+    fv = add(fv, cross(u, sub(pf, pk[k])));
   }
   // the slide of a finger along the hand's y axis (a solver DOF of its own in finger_dynamics mode)
-  if (f >= 8 && !c->finger_dynamics) fv = madd(fv, mk(S.s.frot[7][1], S.s.frot[7][4], S.s.frot[7][7]), e.qd[f - 1]);
+  if (f >= 8 && !fdyn) fv = madd(fv, yax, qdf);
+  float fmot = (len(fv) + len(fw) * fext) * dt;
+  if (f >= 8 && fdyn) fmot += fabsr(qdf) * dt;
   st3(S.s.fv[f], fv); st3(S.s.fw[f], fw);
-  S.s.fmot[f] = (len(fv) + len(fw) * S.s.fext[f]) * c->dt;
-  if (f >= 8 && c->finger_dynamics) S.s.fmot[f] += fabsr(e.qd[f - 1]) * c->dt;
+  S.s.fmot[f] = fmot;
 }
 RV_DEV int sim_substep_light(Shared& S, const Consts& K) {
   const rv_config* c = K.cfg;
@@ -3349,22 +3473,20 @@ RV_DEV int sim_substep_light(Shared& S, const Consts& K) {
   if (near_any) {
     // stage 2a: world hull vertices of the flagged sleepers, and the vertices of the boxes near them
     RV_LANES_BEGIN
-      for (int item = lane; item < RV_NCOL * 8; item += 64) {
-        const int col = item >> 3;
+      VertexLoads V; v3 bpos[RV_MAXB]; m3 brot[RV_MAXB];
+#pragma unroll
+      for (int b = 0; b < RV_MAXB; ++b) hull_vertex_load(S, K, lane, b, S.s.bnear[b], V);
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        const int item = lane + 64 * t, col = item < RV_NCOL * 8 ? item >> 3 : 0;
         int nd = 0;
 #pragma unroll
         for (int b = 0; b < RV_MAXB; ++b) nd |= S.s.nearf[b][col];
-        if (nd) arm_box_vertex(S, K, col, item & 7);
+        box_vertex_load(S, K, lane, t, item < RV_NCOL * 8 && nd, V);
       }
-      for (int item = lane; item < RV_MAXB * RV_MAXH * RV_MAXV; item += 64) {
-        int b = item / (RV_MAXH * RV_MAXV), h = (item / RV_MAXV) % RV_MAXH, i = item % RV_MAXV;
-        if (!S.s.bnear[b]) continue;
-        if (h >= S.n_hulls[b] || i >= S.n_verts[b][h]) continue;
-        const rv_shape* s = &K.scene->shapes[S.e.shape[b]];
-        float sc = S.e.scale[b];
-        v3 l = mk(s->verts[h][i][0] * sc, s->verts[h][i][1] * sc, s->verts[h][i][2] * sc);
-        st3(S.s.u.r.wv[b][h][i], add(ld3(S.e.body[b]), mulv(qmat(ldq(S.e.body[b] + 3)), l)));
-      }
+#pragma unroll
+      for (int b = 0; b < RV_MAXB; ++b) { bpos[b] = ld3(S.e.body[b]); brot[b] = qmat(ldq(S.e.body[b] + 3)); }
+      vertex_stores(S, lane, V, bpos, brot);
     RV_LANES_END
     // stage 2b: one 16-lane group per body runs the distance queries, box by box
     RV_LANES_BEGIN
@@ -3445,29 +3567,50 @@ RV_DEV int sim_substep_light(Shared& S, const Consts& K) {
 #if !RV_ON_DEVICE
       wake_me = S.s.ready[lane];
 #endif
-      if (S.s.wake[b] || wake_me) {
+      // (loads first, stores last: DESIGN.md §10, "LDS staging".  The wake-up writes e.asleep, which body_on reads: forwarded)
+      const int woken = S.s.wake[b] || wake_me;
+      const int present = e.active[b] && !e.frozen[b], asleep0 = e.asleep[b];
+      const int is_static = body_static(e, b);
+      float bs[13];
+#pragma unroll
+      for (int k = 0; k < 13; ++k) bs[k] = e.body[b][k];
+      const float ii[3] = {e.inv_inertia[b][0], e.inv_inertia[b][1], e.inv_inertia[b][2]};
+      const float radius = e.radius[b];
+      const float dt = c->dt, gx = c->gravity_xy[0], gy = c->gravity_xy[1], gz = c->gravity_z, lin_damp = c->lin_damp, ang_damp = c->ang_damp;
+      // ---- arithmetic on the locals
+      const int on = present && !(woken ? 0 : asleep0);
+      v3 v = mk(0, 0, 0), w = mk(0, 0, 0); float mot = 0.0f;      // (no gravity on a static body; its velocities stay zero)
+      m3 m; float iinv[9];
+      if (on) {
+        if (!is_static) {
+          bs[7] += gx * dt; bs[8] += gy * dt;
+          bs[9] += gz * dt;
+          v = scale(mk(bs[7], bs[8], bs[9]), lin_damp);
+          w = scale(mk(bs[10], bs[11], bs[12]), ang_damp);
+          mot = (len(v) + len(w) * radius) * dt;
+        }
+        q4 bq; bq.x = bs[3]; bq.y = bs[4]; bq.z = bs[5]; bq.w = bs[6];
+        m = qmat(bq);
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+          for (int cc2 = 0; cc2 < 3; ++cc2)
+            iinv[r * 3 + cc2] = m.m[r * 3 + 0] * ii[0] * m.m[cc2 * 3 + 0] + m.m[r * 3 + 1] * ii[1] * m.m[cc2 * 3 + 1] + m.m[r * 3 + 2] * ii[2] * m.m[cc2 * 3 + 2];
+      }
+      // ---- stores
+      if (woken) {
         e.asleep[b] = 0; e.sleep_count[b] = 0; e.deact_count[b] = 0;
         // open the pose window at the pose it was resting in
         e.still_count[b] = 1; e.undisturbed[b] = 1;
-        st3(e.still_ref[b], ld3(e.body[b])); stq(e.still_ref[b] + 3, ldq(e.body[b] + 3));
+#pragma unroll
+        for (int k = 0; k < 7; ++k) e.still_ref[b][k] = bs[k];
       }
-      if (body_on(e, b)) {
-        float dt = c->dt;
-        if (body_static(e, b)) S.s.mot[b] = 0.0f;      // (no gravity on a static body; its velocities stay zero)
-        else {
-        e.body[b][7] += c->gravity_xy[0] * dt; e.body[b][8] += c->gravity_xy[1] * dt;
-        e.body[b][9] += c->gravity_z * dt;
-        v3 v = scale(ld3(e.body[b] + 7), c->lin_damp);
-        v3 w = scale(ld3(e.body[b] + 10), c->ang_damp);
-        st3(e.body[b] + 7, v); st3(e.body[b] + 10, w);
-        S.s.mot[b] = (len(v) + len(w) * e.radius[b]) * dt;
-        }
-        m3 m = qmat(ldq(e.body[b] + 3));
+      if (on) {
+        if (!is_static) { st3(e.body[b] + 7, v); st3(e.body[b] + 10, w); }
+        S.s.mot[b] = mot;
         stm(S.s.rot[b], m);
-        const float* ii = e.inv_inertia[b];
-        for (int r = 0; r < 3; ++r)
-          for (int cc2 = 0; cc2 < 3; ++cc2)
-            S.s.iinv[b][r * 3 + cc2] = m.m[r * 3 + 0] * ii[0] * m.m[cc2 * 3 + 0] + m.m[r * 3 + 1] * ii[1] * m.m[cc2 * 3 + 1] + m.m[r * 3 + 2] * ii[2] * m.m[cc2 * 3 + 2];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) S.s.iinv[b][k] = iinv[k];
       }
     }
   RV_LANES_END
@@ -3549,23 +3692,35 @@ RV_DEV void sim_substep_heavy(Shared& S, const Consts& K) {
       const int owner = lane;
       OwnerInfo o;
       owner_decode(S, K, owner, arm_on, o);
-      if (o.clear) e.man[o.mi].n = 0;
       int n_pairs = o.n_outer * o.n_inner;
+      // (loads first, stores last: DESIGN.md §10, "LDS staging".  o.a is a collider box for the arm-table detectors, which
+      // are never live: the index is clamped)
+      DevMan& m = e.man[o.mi];
+      const int n0 = m.n; const float acc0 = m.acc;
+      float rfd[4]; int rfr[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) { rfd[i] = S.s.rf_dist[o.mi * 4 + i]; rfr[i] = S.s.rf_rm[o.mi * 4 + i]; }
+      const float mot_a = S.s.mot[o.live ? o.a : 0], mot_b = S.s.mot[o.b >= 0 ? o.b : 0];
+      float fmot[RV_NFRAME];
+#pragma unroll
+      for (int f = 0; f < RV_NFRAME; ++f) fmot[f] = S.s.fmot[f];
+      const int np_max_age = c->np_max_age, sim_steps = e.sim_steps; const float np_gate = c->np_gate;
+      if (o.clear) m.n = 0;
       if (o.live) {
-        DevMan& m = e.man[o.mi];
-        const int lost = refresh_apply(m, &S.s.rf_dist[o.mi * 4], &S.s.rf_rm[o.mi * 4]);
+        const int lost = refresh_apply(m, n0, rfd, rfr);
+        const int n = n0 - lost;
         // narrow-phase gating on the travel of the two shapes since the last full pass
-        float mo = S.s.mot[o.a];
+        float mo = mot_a;
         if (owner >= RV_MAXB + RV_NBB) {
           float am = 0.0f;
 #pragma unroll
-          for (int f = 0; f < RV_NFRAME; ++f) am = fmaxr(am, S.s.fmot[f]);
+          for (int f = 0; f < RV_NFRAME; ++f) am = fmaxr(am, fmot[f]);
           mo = mo + am;
         }
-        if (o.b >= 0) mo = mo + S.s.mot[o.b];
-        float acc = m.acc + mo;
+        if (o.b >= 0) mo = mo + mot_b;
+        float acc = acc0 + mo;
         // (a body on fewer than three support points is rocking or tipping: its support is looked at every substep)
-        const int run = (c->np_max_age <= 0) || m.n == 0 || (owner < RV_MAXB && m.n < 3) || lost > 0 || acc > c->np_gate || (e.sim_steps % c->np_max_age) == 0;
+        const int run = (np_max_age <= 0) || n == 0 || (owner < RV_MAXB && n < 3) || lost > 0 || acc > np_gate || (sim_steps % np_max_age) == 0;
         if (run) acc = 0.0f; else n_pairs = 0;
         m.acc = acc;
       }
@@ -3649,27 +3804,24 @@ RV_DEV void sim_substep_heavy(Shared& S, const Consts& K) {
     }
     if (any) {
       RV_LANES_BEGIN
-        if (arm_on) {
-          for (int item = lane; item < RV_NCOL * 8; item += 64) {
-            const int col = item >> 3;
-            int nd = S.s.atflag[col];
+        VertexLoads V; v3 bpos[RV_MAXB]; m3 brot[RV_MAXB];
 #pragma unroll
-            for (int b = 0; b < RV_MAXB; ++b) nd |= S.s.cn[b][col];
-            if (nd) arm_box_vertex(S, K, col, item & 7);
-          }
+        for (int b = 0; b < RV_MAXB; ++b) hull_vertex_load(S, K, lane, b, S.s.wvneed[b], V);
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+          const int item = lane + 64 * t, col = item < RV_NCOL * 8 ? item >> 3 : 0;
+          int nd = S.s.atflag[col];
+#pragma unroll
+          for (int b = 0; b < RV_MAXB; ++b) nd |= S.s.cn[b][col];
+          box_vertex_load(S, K, lane, t, arm_on && item < RV_NCOL * 8 && nd, V);
         }
+#pragma unroll
         for (int b = 0; b < RV_MAXB; ++b) {
-          if (!S.s.wvneed[b]) continue;
-          const rv_shape* s = &K.scene->shapes[S.e.shape[b]];
-          const float sc = S.e.scale[b];
-          const int n_items = S.n_hulls[b] * RV_MAXV;
-          for (int item = lane; item < n_items; item += 64) {
-            const int h = item / RV_MAXV, i = item % RV_MAXV;
-            if (i >= S.n_verts[b][h]) continue;
-            v3 l = mk(s->verts[h][i][0] * sc, s->verts[h][i][1] * sc, s->verts[h][i][2] * sc);
-            st3(S.s.u.r.wv[b][h][i], add(ld3(S.e.body[b]), mulv(S.s.rot[b], l)));
-          }
+          bpos[b] = ld3(S.e.body[b]);
+#pragma unroll
+          for (int k = 0; k < 9; ++k) brot[b].m[k] = S.s.rot[b][k];
         }
+        vertex_stores(S, lane, V, bpos, brot);
       RV_LANES_END
     }
   }
@@ -4078,83 +4230,124 @@ RV_DEV void sim_substep_heavy(Shared& S, const Consts& K) {
   // integrate positions, freeze fallen bodies, counters
   RV_LANES_BEGIN
     DevEnv& e = S.e;
+    // (loads first, stores last: DESIGN.md §10, "LDS staging".  Every value the phase wrote and read again -- the spin after
+    // rolling friction, frozen, the three counters, the pose window -- is carried in a register)
+    int steps0 = 0, steps1 = 0;
+    if (lane == 32) { steps0 = e.sim_steps; steps1 = e.substeps_last; }
     if (lane < RV_MAXB) {
       int b = lane;
-      if (body_on(e, b)) {
-        float dt = c->dt;
+      const int on = body_on(e, b), is_static = body_static(e, b);
+      float bs[13];
+#pragma unroll
+      for (int k = 0; k < 13; ++k) bs[k] = e.body[b][k];
+      const DevMan& mt = e.man[RV_TIDX(b)];
+      const int mtn = mt.n;
+      const float mln[4] = {mt.ln[0], mt.ln[1], mt.ln[2], mt.ln[3]};
+      float iinv[9];
+#pragma unroll
+      for (int k = 0; k < 9; ++k) iinv[k] = S.s.iinv[b][k];
+      int sleep_count = e.sleep_count[b], still_count = e.still_count[b], undisturbed = e.undisturbed[b], deact_count = e.deact_count[b];
+      int frozen = e.frozen[b];
+      float sref[7];
+#pragma unroll
+      for (int k = 0; k < 7; ++k) sref[k] = e.still_ref[b][k];
+      const int man_a_n = e.man[RV_AIDX(b)].n;
+      int nbb[RV_NBB];
+#pragma unroll
+      for (int k = 0; k < RV_NBB; ++k) nbb[k] = e.man[RV_BBIDX(k)].n;
+      const int tied = con_pair_member(e, b);
+      const float dt = c->dt, rolling_friction = c->rolling_friction, ground_z = c->ground_z, fall_depth = c->fall_depth;
+      const float sleep_lin = c->sleep_lin, sleep_ang = c->sleep_ang, sleep_pos_win = c->sleep_pos_win, sleep_rot_win = c->sleep_rot_win;
+      const float deact_lin = c->deact_lin, deact_ang = c->deact_ang;
+      const int sleep_steps = c->sleep_steps, deact_steps = c->deact_steps, finger_dynamics = c->finger_dynamics;
+      if (on) {
+        // ---- arithmetic on the locals
         // rolling / spinning friction on the support: a resisting angular impulse of at most
         // rolling_friction x (normal impulse of the table manifold), never reversing the spin
-        if (c->rolling_friction > 0.0f && e.man[RV_TIDX(b)].n > 0) {
-          const DevMan& mt = e.man[RV_TIDX(b)];
+        int spun = 0;
+        if (rolling_friction > 0.0f && mtn > 0) {
           float nimp = 0.0f;
-          for (int i = 0; i < mt.n; ++i) nimp += mt.ln[i];
-          v3 w0 = ld3(e.body[b] + 10);
+#pragma unroll
+          for (int i = 0; i < 4; ++i) if (i < mtn) nimp += mln[i];
+          v3 w0 = mk(bs[10], bs[11], bs[12]);
           float wl = len(w0);
           if (wl > 0.0f && nimp > 0.0f) {
             v3 dir = scale(w0, 1.0f / wl);
-            v3 iw = mulv(S.s.iinv[b], dir);
+            v3 iw = mulv(iinv, dir);
             float k = dot(dir, iw);
-            float j = fminr(c->rolling_friction * nimp, wl / k);
-            st3(e.body[b] + 10, madd(w0, iw, -j));
+            float j = fminr(rolling_friction * nimp, wl / k);
+            const v3 w1 = madd(w0, iw, -j);
+            bs[10] = w1.x; bs[11] = w1.y; bs[12] = w1.z; spun = 1;
           }
         }
-        v3 v = ld3(e.body[b] + 7), w = ld3(e.body[b] + 10);
-        v3 p = ld3(e.body[b]);
-        q4 q = ldq(e.body[b] + 3);
-        if (!body_static(e, b)) {      // (a static body stays where it is: its velocities are zero, no impulse changes them)
+        v3 v = mk(bs[7], bs[8], bs[9]), w = mk(bs[10], bs[11], bs[12]);
+        v3 p = mk(bs[0], bs[1], bs[2]);
+        q4 q; q.x = bs[3]; q.y = bs[4]; q.z = bs[5]; q.w = bs[6];
+        int fell = 0;
+        if (!is_static) {      // (a static body stays where it is: its velocities are zero, no impulse changes them)
         p = madd(p, v, dt);
-        st3(e.body[b], p);
         q4 wq; wq.x = w.x; wq.y = w.y; wq.z = w.z; wq.w = 0.0f;
         q4 dq = qmul(wq, q);
         q.x += 0.5f * dt * dq.x; q.y += 0.5f * dt * dq.y; q.z += 0.5f * dt * dq.z; q.w += 0.5f * dt * dq.w;
         q = qnormalize(q);
-        stq(e.body[b] + 3, q);
-        if (p.z < c->ground_z - c->fall_depth) {
-          e.frozen[b] = 1;
-          st3(e.body[b] + 7, mk(0, 0, 0)); st3(e.body[b] + 10, mk(0, 0, 0));
-        }
+        if (p.z < ground_z - fall_depth) { fell = 1; frozen = 1; }
         }
         // substeps in a row below the sleep thresholds (the deactivation counter; also what makes a row a 'rest' row of the solver)
-        if (dot(v, v) < c->sleep_lin * c->sleep_lin && dot(w, w) < c->sleep_ang * c->sleep_ang) e.sleep_count[b]++;
-        else { e.sleep_count[b] = 0; }
-        if (c->sleep_steps > 0) {
+        if (dot(v, v) < sleep_lin * sleep_lin && dot(w, w) < sleep_ang * sleep_ang) sleep_count++;
+        else { sleep_count = 0; }
+        int inside = 0, ready = 0;
+        if (sleep_steps > 0) {
           // in-place oscillation: the pose has not left a small window around where
           // it was when the window opened
-          if (c->sleep_pos_win > 0.0f) {
-            int inside = 0;
-            if (e.still_count[b] > 0) {
-              v3 dp = sub(p, ld3(e.still_ref[b]));
-              float dqm = fmaxr(fmaxr(fmaxr(fmaxr(0.0f, fabsr(q.x - e.still_ref[b][3])), fabsr(q.y - e.still_ref[b][4])),
-                                      fabsr(q.z - e.still_ref[b][5])), fabsr(q.w - e.still_ref[b][6]));
-              inside = dot(dp, dp) < c->sleep_pos_win * c->sleep_pos_win && dqm < c->sleep_rot_win;
+          if (sleep_pos_win > 0.0f) {
+            if (still_count > 0) {
+              v3 dp = sub(p, mk(sref[0], sref[1], sref[2]));
+              float dqm = fmaxr(fmaxr(fmaxr(fmaxr(0.0f, fabsr(q.x - sref[3])), fabsr(q.y - sref[4])),
+                                      fabsr(q.z - sref[5])), fabsr(q.w - sref[6]));
+              inside = dot(dp, dp) < sleep_pos_win * sleep_pos_win && dqm < sleep_rot_win;
             }
-            if (inside) e.still_count[b]++;
-            else { e.undisturbed[b] = 0; e.still_count[b] = 1; st3(e.still_ref[b], p); stq(e.still_ref[b] + 3, q); }
+            if (inside) still_count++;
+            else { undisturbed = 0; still_count = 1; }
           }
           // a sleeper that was woken but never left the pose it was resting in goes back
           // to sleep after a quarter of the usual wait
-          const int quick = e.undisturbed[b] && 4 * e.still_count[b] >= c->sleep_steps && 4 * e.sleep_count[b] >= c->sleep_steps;
+          const int quick = undisturbed && 4 * still_count >= sleep_steps && 4 * sleep_count >= sleep_steps;
           // a body the force-limited gripper holds stays active (its island contains the moving fingers)
-          const int held = (c->finger_dynamics && e.man[RV_AIDX(b)].n > 0) || con_pair_member(e, b);
+          const int held = (finger_dynamics && man_a_n > 0) || tied;
           // Bullet's own rule (0.8 m/s, 1 rad/s, 2 s) for a body whose island is the body alone:
           // no arm contact points, no contact points with another awake body
           int deact = 0;
-          if (c->deact_steps > 0) {
-            int free_ = e.man[RV_AIDX(b)].n == 0;
+          if (deact_steps > 0) {
+            int free_ = man_a_n == 0;
 #pragma unroll
             for (int k = 0; k < RV_NBB; ++k) {
               const int a_ = bb_a(k), b_ = bb_b(k);
-              if ((a_ == b || b_ == b) && e.man[RV_BBIDX(k)].n != 0 && ((on_mask >> (a_ == b ? b_ : a_)) & 1)) free_ = 0;
+              if ((a_ == b || b_ == b) && nbb[k] != 0 && ((on_mask >> (a_ == b ? b_ : a_)) & 1)) free_ = 0;
             }
-            if (free_ && dot(v, v) < c->deact_lin * c->deact_lin && dot(w, w) < c->deact_ang * c->deact_ang) e.deact_count[b]++;
-            else e.deact_count[b] = 0;
-            deact = e.deact_count[b] >= c->deact_steps;
+            if (free_ && dot(v, v) < deact_lin * deact_lin && dot(w, w) < deact_ang * deact_ang) deact_count++;
+            else deact_count = 0;
+            deact = deact_count >= deact_steps;
           }
-          S.s.ready[b] = e.frozen[b] || (!held && (e.sleep_count[b] >= c->sleep_steps || e.still_count[b] >= c->sleep_steps || quick || deact));
+          ready = frozen || (!held && (sleep_count >= sleep_steps || still_count >= sleep_steps || quick || deact));
+        }
+        // ---- stores
+        if (!is_static) { st3(e.body[b], p); stq(e.body[b] + 3, q); }
+        if (fell) {
+          e.frozen[b] = 1;
+          st3(e.body[b] + 7, mk(0, 0, 0)); st3(e.body[b] + 10, mk(0, 0, 0));
+        } else if (spun) st3(e.body[b] + 10, w);
+        e.sleep_count[b] = sleep_count;
+        if (sleep_steps > 0) {
+          if (sleep_pos_win > 0.0f) {
+            e.still_count[b] = still_count;
+            if (!inside) { e.undisturbed[b] = 0; st3(e.still_ref[b], p); stq(e.still_ref[b] + 3, q); }
+          }
+          if (deact_steps > 0) e.deact_count[b] = deact_count;
+          S.s.ready[b] = ready;
         }
       }
     }
-    if (lane == 32) { e.sim_steps++; e.substeps_last++; }
+    if (lane == 32) { e.sim_steps = steps0 + 1; e.substeps_last = steps1 + 1; }
 #if RV_ON_DEVICE
   }
   // islands go to sleep as a whole: a body sleeps when every awake body it is coupled to
