@@ -464,6 +464,42 @@ int  rv_plan_reward(rv_world* w, const rv_plan_params* h_params, const float* d_
 int  rv_plan_score(rv_world* w, const rv_plan_params* h_params, const float* d_state0, const float* d_plans,
                    int32_t s, int32_t h, float* d_returns /* [N][s] */, int32_t* d_lengths /* [N][s] */, int32_t* d_best /* [N] */);
 
+/* ---- env states as data: save, restore, branch, and look-ahead with the simulator itself (no counterpart in the
+ *      reference, whose planners get their candidate states from a learned dynamics model).  One env is one block of
+ *      rv_state_bytes() bytes that holds no pointer and no env id: the bodies, the arm, its targets, the contact
+ *      manifolds, the counters, the last observation and reward, the pending action and -- for an env that
+ *      rv_step_poll left in the middle of an env.step() -- the step's progress.  Copying the block is copying the env;
+ *      a restored env continues bit for bit as the saved one would have (every random draw is keyed by seed, global env
+ *      id and the counters in the block; an env.step() with given actions draws nothing).  NOT in a block, hence neither
+ *      saved nor branched: rv_set_auto_reset, the stream, the statistics of the last launch, the task-queue buffers.
+ *      Blocks are only meaningful to the build that wrote them (rv_source_hash) and to worlds with the same rv_config
+ *      apart from n_envs and env_id_offset.  Point clouds are sampled with the global env id of the env that is
+ *      observed, so those of a branch differ from its source's; poses, rewards and depth renders do not.
+ *      STREAM ORDERING: every call is asynchronous on the stream of the world that is WRITTEN (rv_state_save: the
+ *      world that is read, into the caller's buffer).  rv_branch / rv_plan_simulate with two worlds on different
+ *      streams: the copy waits, through an event, for everything the source's stream was given before the call, and
+ *      the source's stream waits for the copy before it runs anything given to it after the call -- the source may be
+ *      stepped right away.  Buffers the caller passes are ordered by the caller, as everywhere in this header. ---- */
+int64_t rv_state_bytes(const rv_world* w);   /* bytes of one env block of the loaded build */
+/* the N blocks of the world to d_buf (N x rv_state_bytes bytes, 4-byte aligned) */
+int  rv_state_save(rv_world* w, void* d_buf);
+/* env j takes block d_index[j] of the n_blocks blocks in d_buf; d_index == NULL: block j, and n_blocks must be N.  Index
+ * -1 leaves env j as it is, and so does any other index outside [0, n_blocks): nothing outside the buffer is read. */
+int  rv_state_load(rv_world* w, const void* d_buf, int32_t n_blocks, const int32_t* d_index /* [N] or NULL */);
+/* env j of dst becomes a copy of env j / s of src: dst needs s x the envs of src.  RV_ERR_VALUE (and nothing changes)
+ * unless the two rv_configs are equal apart from n_envs and env_id_offset and the worlds were made from the same
+ * rv_scene on the same device.  The two may launch different builds of the env kernel (rv_env_kernel_build). */
+int  rv_branch(rv_world* dst, rv_world* src, int32_t s);
+/* s candidate action sequences of h steps for each of the N envs of src, tried out on the plan world (N x s envs):
+ * rv_branch(plan, src, s), then h times { the actions of step t (as rv_set_actions); rv_step_macro; record }.  src is
+ * only read.  d_actions [N][s][h][G][4]; d_states [N][s][h][RV_MAXB][2] (8-byte aligned) the xy of every body's
+ * observed position after each step, zeros for absent bodies -- the d_plans of rv_plan_score, for any n_bodies;
+ * d_rewards / d_dones [N][s][h] as rv_reward reports them after each step.  A branch whose episode ended earlier is
+ * not stepped again: its later rows repeat its last state with reward 0, done 1.  Any output may be NULL.  PushEnv
+ * worlds only; the conditions of rv_branch; h >= 1. */
+int  rv_plan_simulate(rv_world* plan, rv_world* src, const float* d_actions, int32_t s, int32_t h,
+                      float* d_states, float* d_rewards, uint8_t* d_dones);
+
 /* ---- Simulator.step x n (simulator.py:94-103): ControllableBody.update +
  *      BulletPhysics.step (bullet_physics.py:106-109), no phase machine. ---- */
 int  rv_step_sub(rv_world* w, int32_t n_substeps);

@@ -213,6 +213,33 @@ class rv_plan_params(C.Structure):
     ]
 
 
+# the env-state entry points of include/rovat.h (rv_state_* / rv_branch / rv_plan_simulate): name -> (restype, argtypes);
+# lib.load() binds them from here.  Worlds and device buffers are void pointers.
+STATE_API = {
+    'rv_state_bytes': (i64, [C.c_void_p]),
+    'rv_state_save': (C.c_int, [C.c_void_p, C.c_void_p]),
+    'rv_state_load': (C.c_int, [C.c_void_p, C.c_void_p, i32, C.c_void_p]),
+    'rv_branch': (C.c_int, [C.c_void_p, C.c_void_p, i32]),
+    'rv_plan_simulate': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, i32, i32, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
+
+def bind_state_api(handle):
+    """restype / argtypes of the STATE_API functions on a loaded librovat_hip.so"""
+    for name, (res, args) in STATE_API.items():
+        fn = getattr(handle, name)
+        fn.restype, fn.argtypes = res, list(args)
+
+
+def config_key(cfg):
+    """The bytes of an rv_config that two worlds must share to exchange env blocks: everything but n_envs and
+    env_id_offset (rv_branch compares the same)."""
+    c = rv_config.from_buffer_copy(bytes(cfg))
+    c.n_envs = 0
+    c.env_id_offset = 0
+    return bytes(c)
+
+
 def assign(arr, values):
     """Copy a (nested) python/numpy sequence into a ctypes array."""
     for i, v in enumerate(values):

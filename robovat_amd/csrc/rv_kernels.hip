@@ -29,6 +29,7 @@
 using namespace rv;
 
 #include "rv_env_kernel.h"
+#include "rv_dev_state.h"
 
 #define ENV_THREAD() const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x); if (i >= n) return; DevEnv& e = envs[i];
 
@@ -573,6 +574,9 @@ struct rv_world {
   int q_grid; int* d_q; size_t q_cap; int q_launch; bool q_used;
   // rv_policy_antipodal: the depth it renders itself, the per-env filter scratch (floats; grown on demand)
   float* d_ap_depth; size_t ap_depth_cap; float* d_ap_scratch; size_t ap_scratch_cap;
+  // rv_branch / rv_plan_simulate: FNV-1a of the rv_scene the world was made from (two worlds may exchange env blocks only
+  // when they share it), and the event that orders a copy between the streams of two worlds
+  uint64_t scene_hash; hipEvent_t ev_state;
 };
 
 static thread_local std::string g_err;
@@ -719,6 +723,54 @@ static void launch_plan_score(rv_world* w, const PlanArgs& a, int tpb) {
   hipLaunchKernelGGL((k_plan_score<B, V4>), dim3((unsigned)w->n), dim3((unsigned)tpb), 0, w->stream, w->d_envs, w->d_cfg, a);
 }
 
+// ---- env states as data (rv_dev_state.h)
+static uint64_t bytes_hash(const void* p, size_t n) {      // FNV-1a
+  const unsigned char* b = (const unsigned char*)p;
+  uint64_t h = 1469598103934665603ull;
+  for (size_t i = 0; i < n; ++i) { h ^= b[i]; h *= 1099511628211ull; }
+  return h;
+}
+// block j of dst (n_dst blocks) takes block index[j] (NULL: j / s) of src (n_src blocks), on `st`.  16-byte accesses where
+// the block size and both bases allow them.  (The grid's y extent ends at 65535: larger worlds take several launches.)
+static int launch_gather(hipStream_t st, void* dst, const void* src, int n_dst, int n_src, const int32_t* index, int s) {
+  const bool v4 = RV_STATE_VEC_OK && aligned_to(dst, 16) && aligned_to(src, 16);
+  for (int j0 = 0; j0 < n_dst; j0 += 65535) {
+    const int rows = n_dst - j0 < 65535 ? n_dst - j0 : 65535;
+    if (v4) hipLaunchKernelGGL(k_env_blocks_gather<true>, dim3(1u, (unsigned)rows), dim3(RV_STATE_TPB), 0, st, (uint32_t*)dst, (const uint32_t*)src, j0, n_dst, n_src, index, s);
+    else hipLaunchKernelGGL(k_env_blocks_gather<false>, dim3(1u, (unsigned)rows), dim3(RV_STATE_TPB), 0, st, (uint32_t*)dst, (const uint32_t*)src, j0, n_dst, n_src, index, s);
+    HIPCHK(hipGetLastError());
+  }
+  return RV_OK;
+}
+// identity copies of whole worlds go through the runtime's device-to-device copy or through the gather kernel:
+// RV_STATE_MEMCPY = 1 / 0 forces one (read per call: tools/state_branch_bench.py measures both in one process)
+static bool state_identity_by_runtime() {
+  const char* f = getenv("RV_STATE_MEMCPY");
+  return f ? atoi(f) != 0 : RV_STATE_IDENTITY_BY_RUNTIME != 0;
+}
+// what rv_branch and rv_plan_simulate ask of their two worlds; nothing has been launched when this fails
+static int branch_check(const rv_world* dst, const rv_world* src, int s, const char* who) {
+  const std::string me(who);
+  if (dst == src) return fail(RV_ERR_VALUE, me + ": the two worlds must differ");
+  if (s < 1) return fail(RV_ERR_VALUE, me + ": s must be positive");
+  if ((long long)dst->n != (long long)src->n * (long long)s) return fail(RV_ERR_VALUE, me + ": the destination needs n_envs = s x the source's n_envs");
+  if (dst->device != src->device) return fail(RV_ERR_VALUE, me + ": the two worlds live on different devices");
+  if (dst->scene_hash != src->scene_hash) return fail(RV_ERR_VALUE, me + ": the two worlds were made from different scenes");
+  rv_config a = dst->cfg, b = src->cfg;
+  a.n_envs = b.n_envs = 0; a.env_id_offset = b.env_id_offset = 0;
+  if (memcmp(&a, &b, sizeof(rv_config)) != 0) return fail(RV_ERR_VALUE, me + ": the two worlds differ in more of rv_config than n_envs and env_id_offset");
+  return RV_OK;
+}
+// env j of dst = env j / s of src.  dst's stream waits for what src's stream has been given so far; src's stream waits for
+// the copy before it goes on (it may change the blocks next)
+static int branch_copy(rv_world* dst, rv_world* src, int s) {
+  const bool cross = dst->stream != src->stream;
+  if (cross) { HIPCHK(hipEventRecord(dst->ev_state, src->stream)); HIPCHK(hipStreamWaitEvent(dst->stream, dst->ev_state, 0)); }
+  int rc = launch_gather(dst->stream, dst->d_envs, src->d_envs, dst->n, src->n, nullptr, s); if (rc != RV_OK) return rc;
+  if (cross) { HIPCHK(hipEventRecord(dst->ev_state, dst->stream)); HIPCHK(hipStreamWaitEvent(src->stream, dst->ev_state, 0)); }
+  return RV_OK;
+}
+
 extern "C" {
 
 const char* rv_last_error(void) { return g_err.c_str(); }
@@ -742,6 +794,7 @@ int rv_create(const rv_config* cfg, const rv_scene* scene, int device, rv_world*
   w->cfg = *cfg; w->device = device; w->n = cfg->n_envs; w->stream = nullptr; w->timed = false;
   w->d_snaps = nullptr; w->n_snaps_cap = 0;
   w->d_ap_depth = nullptr; w->ap_depth_cap = 0; w->d_ap_scratch = nullptr; w->ap_scratch_cap = 0;
+  w->scene_hash = bytes_hash(scene, sizeof(rv_scene));
   {
     // one wave per env: with more envs than SIMDs the two-waves-per-SIMD build of the env kernel pays
     // (RV_ENV_OCC=1 / 2 in the environment forces a build: measurements)
@@ -769,6 +822,7 @@ int rv_create(const rv_config* cfg, const rv_scene* scene, int device, rv_world*
   HIPCHK(hipMemset(w->d_stats, 0, sizeof(rv_macro_stats)));
   HIPCHK(hipEventCreate(&w->ev0));
   HIPCHK(hipEventCreate(&w->ev1));
+  HIPCHK(hipEventCreateWithFlags(&w->ev_state, hipEventDisableTiming));
   hipLaunchKernelGGL(k_init, grid1(w->n), dim3(TPB), 0, w->stream, w->d_envs, w->n, cfg->arm_friction, cfg->table_friction, w->d_cfg);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(w->stream));
@@ -785,7 +839,7 @@ int rv_destroy(rv_world* w) {
   if (w->d_snaps) (void)hipFree(w->d_snaps);
   if (w->d_ap_depth) (void)hipFree(w->d_ap_depth);
   if (w->d_ap_scratch) (void)hipFree(w->d_ap_scratch);
-  (void)hipEventDestroy(w->ev0); (void)hipEventDestroy(w->ev1);
+  (void)hipEventDestroy(w->ev0); (void)hipEventDestroy(w->ev1); (void)hipEventDestroy(w->ev_state);
   delete w;
   return RV_OK;
 }
@@ -1135,6 +1189,49 @@ int rv_plan_score(rv_world* w, const rv_plan_params* h_params, const float* d_st
   const bool v4 = aligned_to(d_plans, 16);
   PLAN_DISPATCH(a.p.n_bodies, v4, launch_plan_score, w, a, tpb);
   HIPCHK(hipGetLastError());
+  return RV_OK;
+}
+int64_t rv_state_bytes(const rv_world* w) { (void)w; return (int64_t)sizeof(DevEnv); }
+int rv_state_save(rv_world* w, void* d_buf) {
+  WCHK(w); NEED(d_buf, "rv_state_save");
+  if (!aligned_to(d_buf, 4)) return fail(RV_ERR_VALUE, "rv_state_save: the buffer must be 4-byte aligned");
+  if (state_identity_by_runtime()) { HIPCHK(hipMemcpyAsync(d_buf, w->d_envs, sizeof(DevEnv) * (size_t)w->n, hipMemcpyDeviceToDevice, w->stream)); return RV_OK; }
+  return launch_gather(w->stream, d_buf, w->d_envs, w->n, w->n, nullptr, 1);
+}
+int rv_state_load(rv_world* w, const void* d_buf, int32_t n_blocks, const int32_t* d_index) {
+  WCHK(w); NEED(d_buf, "rv_state_load");
+  if (!aligned_to(d_buf, 4) || !aligned_to(d_index, 4)) return fail(RV_ERR_VALUE, "rv_state_load: the buffers must be 4-byte aligned");
+  if (n_blocks < 1) return fail(RV_ERR_VALUE, "rv_state_load: n_blocks must be positive");
+  if (!d_index && n_blocks != w->n) return fail(RV_ERR_VALUE, "rv_state_load: without an index the buffer must hold one block per env");
+  if (!d_index && state_identity_by_runtime()) { HIPCHK(hipMemcpyAsync(w->d_envs, d_buf, sizeof(DevEnv) * (size_t)w->n, hipMemcpyDeviceToDevice, w->stream)); return RV_OK; }
+  return launch_gather(w->stream, w->d_envs, d_buf, w->n, n_blocks, d_index, 1);
+}
+int rv_branch(rv_world* dst, rv_world* src, int32_t s) {
+  WCHK(src); WCHK(dst);
+  int rc = branch_check(dst, src, s, "rv_branch"); if (rc != RV_OK) return rc;
+  return branch_copy(dst, src, s);
+}
+int rv_plan_simulate(rv_world* plan, rv_world* src, const float* d_actions, int32_t s, int32_t h,
+                     float* d_states, float* d_rewards, uint8_t* d_dones) {
+  WCHK(src); WCHK(plan);
+  rv_world* w = plan;
+  if (src->cfg.env_type == RV_ENV_GRASP || plan->cfg.env_type == RV_ENV_GRASP) return fail(RV_ERR_VALUE, "rv_plan_simulate: PushEnv worlds only");
+  int rc = branch_check(plan, src, s, "rv_plan_simulate"); if (rc != RV_OK) return rc;
+  if (h < 1) return fail(RV_ERR_VALUE, "rv_plan_simulate: h must be positive");
+  NEED(d_actions, "rv_plan_simulate");
+  if (!aligned_to(d_actions, 4) || !aligned_to(d_states, 8) || !aligned_to(d_rewards, 4)) return fail(RV_ERR_VALUE, "rv_plan_simulate: the states must be 8-byte aligned, actions and rewards 4-byte aligned");
+  const int G = w->cfg.num_goal_steps > 0 ? w->cfg.num_goal_steps : 1;
+  if ((long long)w->n * G * 4 > 0x7fffffffLL || (long long)w->n * RV_MAXB > 0x7fffffffLL) return fail(RV_ERR_VALUE, "rv_plan_simulate: too many envs for one launch");
+  rc = branch_copy(plan, src, s); if (rc != RV_OK) return rc;
+  for (int t = 0; t < h; ++t) {
+    hipLaunchKernelGGL(k_plan_actions, dim3((unsigned)((w->n * G * 4 + 255) / 256)), dim3(256), 0, w->stream, w->d_envs, w->n, d_actions, G, (int)h, t);
+    HIPCHK(hipGetLastError());
+    rc = launch_env<MODE_MACRO>(w, nullptr, 0, 0, 0, 0, 0, 0); if (rc != RV_OK) return rc;
+    if (d_states || d_rewards || d_dones) {
+      hipLaunchKernelGGL(k_plan_record, dim3((unsigned)((w->n * RV_MAXB + 255) / 256)), dim3(256), 0, w->stream, w->d_envs, w->n, (int)h, t, d_states, d_rewards, d_dones);
+      HIPCHK(hipGetLastError());
+    }
+  }
   return RV_OK;
 }
 int rv_reward(rv_world* w, float* d_reward, uint8_t* d_done) { WCHK(w); SIMPLE_LAUNCH(k_reward, w->d_envs, w->n, d_reward, d_done); return RV_OK; }

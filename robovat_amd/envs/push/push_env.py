@@ -62,6 +62,7 @@ class VecPushEnv(object):
         self.action_shape = (4,) if g == 0 else (g, 4)
         self.action_space = Box(-1.0, 1.0, self.action_shape)
         self._macro_index = 0
+        self._plan_worlds = {}      # S -> the world of N x S envs that simulate_plans branches into
 
     @property
     def device(self):
@@ -133,6 +134,51 @@ class VecPushEnv(object):
         r, t = self.world.plan_reward(state, next_state, self._plan_params(b, is_high_level))
         return r, t.bool()
 
+    def save_state(self):
+        """All N envs as they are now (``lib.World.save_state``): a ``lib.Snapshot`` on the device, plus the index of the
+        env's next RandomPolicy draw.  An env.step() that ``step_poll`` left unfinished is part of the state."""
+        snap = self.world.save_state()
+        snap.macro_index = self._macro_index
+        return snap
+
+    def restore_state(self, snap, mask=None):
+        """Put the envs back where ``snap`` was taken: all of them, or those flagged in ``mask`` (bool [N]; the others
+        keep their present state).  From then on they continue bit for bit as they did after the snapshot.  (For an env
+        that lives in a Simulator, the host-side Body / Constraint wrappers are not part of a snapshot.)"""
+        if mask is None:
+            self.world.load_state(snap)
+            if getattr(snap, 'macro_index', None) is not None:
+                self._macro_index = snap.macro_index
+            return
+        torch = self.world.torch
+        m = torch.as_tensor(mask, device=self.device).reshape(self.num_envs).bool()
+        ar = torch.arange(self.num_envs, device=self.device, dtype=torch.int32)
+        self.world.load_state(snap, torch.where(m, ar, torch.full_like(ar, -1)))
+
+    def _plan_world(self, s):
+        """the world of N x S envs behind simulate_plans: made on first use and kept per S; same scene, config and seed
+        (rv_create picks the env-kernel build for its size)"""
+        w = self._plan_worlds.get(int(s))
+        if w is None:
+            from robovat_amd import lib
+            cfg = abi.rv_config.from_buffer_copy(bytes(self.rv_config))
+            cfg.n_envs = self.num_envs * int(s)
+            cfg.env_id_offset = int(self.rv_config.env_id_offset) * int(s)
+            w = self._plan_worlds[int(s)] = lib.World(cfg, self.scene, device=self.world.device_index)
+        return w
+
+    def simulate_plans(self, actions):
+        """Look ahead with the simulator: ``actions`` [N, S, H, G, 4] ([N, S, H, 4] without goal steps) are S candidate
+        action sequences of H steps for every env.  Each is tried on a copy of the env (``lib.World.plan_simulate``);
+        the envs themselves do not change.  Returns (states float32 [N, S, H, RV_MAXB, 2]: the observed xy of the bodies
+        after every step, the ``plans`` of ``score_plans``; rewards float32 [N, S, H]; dones bool [N, S, H]).  A
+        candidate whose episode ends early repeats its last state with reward 0, done."""
+        a = self.world.torch.as_tensor(actions)
+        if a.dim() < 2 or int(a.shape[1]) < 1:
+            raise ValueError('simulate_plans: actions must be [N, S, H, G, 4]')
+        st, r, d = self._plan_world(int(a.shape[1])).plan_simulate(self.world, a)
+        return st, r, d.bool()
+
     def rollout(self, n_steps, auto_reset=True, record=True):
         before = self.world.env_counters().cpu().numpy()[:, [2, 4]] if (auto_reset and self._physics is not None) else None
         out = self.world.rollout(n_steps, self._macro_index, auto_reset, record)
@@ -152,6 +198,9 @@ class VecPushEnv(object):
         return self.world.stats()
 
     def close(self):
+        for w in self._plan_worlds.values():
+            w.close()
+        self._plan_worlds = {}
         if self._owns_world:
             self.world.close()
 
@@ -256,6 +305,27 @@ class PushEnv(object):
 
     def plan_rewards(self, state, next_state, is_high_level=False):
         return self._vec.plan_rewards(state, next_state, is_high_level)
+
+    def save_state(self):
+        """``VecPushEnv.save_state`` plus what this wrapper keeps on the host (observations, done flag, returns)."""
+        snap = self._vec.save_state()
+        snap.host = (self._obs_data, self._prev_obs_data, self._done, self._episode_reward, self._total_reward)
+        return snap
+
+    def restore_state(self, snap, mask=None):
+        """``mask``: as ``VecPushEnv.restore_state`` with N = 1 (a false entry restores nothing)."""
+        self._vec.restore_state(snap, mask)
+        if getattr(snap, 'host', None) is not None and (mask is None or bool(np.asarray(mask).reshape(-1)[0])):
+            self._obs_data, self._prev_obs_data, self._done, self._episode_reward, self._total_reward = snap.host
+
+    def simulate_plans(self, actions):
+        """``VecPushEnv.simulate_plans`` for this env: ``actions`` [S, H, G, 4] (or [1, S, H, G, 4]; [S, H, 4] without goal
+        steps).  Returns (states [S, H, RV_MAXB, 2], rewards [S, H], dones [S, H])."""
+        a = self._vec.world.torch.as_tensor(actions)
+        if a.dim() == 2 + len(self._vec.action_shape):
+            a = a[None]
+        st, r, d = self._vec.simulate_plans(a)
+        return st[0], r[0], d[0]
 
     def close(self):
         self._vec.close()

@@ -34,6 +34,7 @@ SYMBOLS = [
     'rv_set_constraint_ex', 'rv_set_link_path', 'rv_get_robot_ready', 'rv_get_camera', 'rv_set_max_joint_velocities',
     'rv_policy_antipodal', 'rv_get_contact_points', 'rv_env_kernel_build',
     'rv_plan_reward', 'rv_plan_score',
+    'rv_state_bytes', 'rv_state_save', 'rv_state_load', 'rv_branch', 'rv_plan_simulate',
 ]
 
 _EXC = {abi.RV_ERR_VALUE: ValueError, abi.RV_ERR_STATE: RuntimeError,
@@ -176,6 +177,7 @@ def load():
                  'rv_set_joint_state', 'rv_get_link_poses', 'rv_get_env_counters',
                  'rv_query_contacts', 'rv_get_manifold_counts', 'rv_get_episode_returns'):
         getattr(lib, name).argtypes = [vp, vp]
+    abi.bind_state_api(lib)
     _lib = lib
     return lib
 
@@ -240,6 +242,22 @@ def check(status):
     if status != abi.RV_OK:
         msg = load().rv_last_error().decode('utf-8', 'replace')
         raise _EXC.get(status, RuntimeError)(msg)
+
+
+class Snapshot(object):
+    """The env blocks of a world at one moment (``World.save_state``): ``blocks`` is a torch uint8 tensor [N, bytes] on
+    the world's device, ``source_hash`` the hash of the sources the library that wrote them was built from, and
+    ``config_key`` the rv_config bytes a world must share to take them (``abi.config_key``: all but n_envs and
+    env_id_offset).  It lives in device memory and only as long as the process: blocks mean nothing to another build."""
+
+    def __init__(self, blocks, source_hash, config_key):
+        self.blocks = blocks
+        self.source_hash = source_hash
+        self.config_key = config_key
+
+    @property
+    def n_blocks(self):
+        return int(self.blocks.shape[0])
 
 
 class World(object):
@@ -487,6 +505,66 @@ class World(object):
         check(self.lib.rv_plan_score(self.h, C.byref(p), None if s0 is None else self._ptr(s0), self._ptr(pl), s, h,
                                      self._ptr(ret), self._ptr(ln), self._ptr(best)))
         return ret, ln, best
+
+    # -- env states as data (include/rovat.h: rv_state_* / rv_branch / rv_plan_simulate)
+    def state_bytes(self):
+        """rv_state_bytes: bytes of one env block of the loaded build."""
+        return int(self.lib.rv_state_bytes(self.h))
+
+    def save_state(self):
+        """rv_state_save: a ``Snapshot`` of all N envs, asynchronous on the world's stream."""
+        buf = self._new((self.n, self.state_bytes()), self.torch.uint8)
+        check(self.lib.rv_state_save(self.h, self._ptr(buf)))
+        return Snapshot(buf, built_source_hash(), abi.config_key(self.cfg))
+
+    def load_state(self, snap, index=None):
+        """rv_state_load: env j takes block ``index[j]`` of the snapshot (None: block j of a snapshot of N blocks; -1: env
+        j stays as it is).  ValueError for a snapshot of another build or config and for an index outside
+        [-1, n_blocks); no env changes then.  (Checking an index reads it back: one sync.)"""
+        if not isinstance(snap, Snapshot):
+            raise ValueError('load_state: not a Snapshot')
+        if snap.source_hash != built_source_hash():
+            raise ValueError('load_state: the snapshot was written by another build of the library')
+        if snap.config_key != abi.config_key(self.cfg):
+            raise ValueError('load_state: the snapshot comes from a world with another config')
+        b = snap.blocks
+        if (b.dim() != 2 or b.dtype != self.torch.uint8 or int(b.shape[1]) != self.state_bytes() or b.device != self.device
+                or not b.is_contiguous()):
+            raise ValueError('load_state: blocks must be a contiguous uint8 [n_blocks, %d] tensor on %s' % (self.state_bytes(), self.device))
+        nb = snap.n_blocks
+        if index is None:
+            if nb != self.n:
+                raise ValueError('load_state: a snapshot of %d blocks needs an index for a world of %d envs' % (nb, self.n))
+            check(self.lib.rv_state_load(self.h, self._ptr(b), nb, None))
+            return
+        idx = self.torch.as_tensor(index, device=self.device)
+        if idx.dtype.is_floating_point or idx.dtype == self.torch.bool or tuple(idx.shape) != (self.n,):
+            raise ValueError('load_state: index must be %d integers' % self.n)
+        if bool(((idx < -1) | (idx >= nb)).any()):
+            raise ValueError('load_state: index outside [-1, %d)' % nb)
+        idx = idx.to(self.torch.int32).contiguous()
+        check(self.lib.rv_state_load(self.h, self._ptr(b), nb, self._ptr(idx)))
+
+    def branch_from(self, src, s):
+        """rv_branch: env j of this world becomes a copy of env j // s of ``src`` (this world has s x its envs)."""
+        check(self.lib.rv_branch(self.h, src.h, int(s)))
+
+    def plan_simulate(self, src, actions):
+        """rv_plan_simulate with this world as the plan world: ``actions`` [N, S, H, G, 4] (N = src.n; [N, S, H, 4] when
+        G = 1) are S action sequences of H steps per env of ``src``, which is only read.  Returns (states float32
+        [N, S, H, RV_MAXB, 2] -- what ``plan_score`` takes --, rewards float32 [N, S, H], dones uint8 [N, S, H])."""
+        a = self.torch.as_tensor(actions, dtype=self.torch.float32, device=self.device)
+        if a.dim() == 4 and self.G == 1:
+            a = a[:, :, :, None]
+        if a.dim() != 5 or int(a.shape[0]) != src.n or tuple(a.shape[3:]) != (self.G, 4) or a.shape[1] < 1 or a.shape[2] < 1:
+            raise ValueError('plan_simulate: actions must be [N, S, H, %d, 4] with N = %d, got %s' % (self.G, src.n, tuple(a.shape)))
+        n, s, h = int(a.shape[0]), int(a.shape[1]), int(a.shape[2])
+        a = a.contiguous()
+        st = self._new((n, s, h, abi.RV_MAXB, 2), self.torch.float32)
+        r = self._new((n, s, h), self.torch.float32)
+        d = self._new((n, s, h), self.torch.uint8)
+        check(self.lib.rv_plan_simulate(self.h, src.h, self._ptr(a), s, h, self._ptr(st), self._ptr(r), self._ptr(d)))
+        return st, r, d
 
     # -- state
     def _get(self, fn, shape, dtype):

@@ -55,3 +55,51 @@ class AntipodalGrasp4DofPolicy(Policy):
             depth = None if observation is None else observation.get('depth')
             return self.env.sample_antipodal_actions(depth, self.config)
         raise NotImplementedError('AntipodalGrasp4DofPolicy needs a Grasp4DofEnv / VecGrasp4DofEnv')
+
+
+class ShootingPushPolicy(Policy):
+    """Random-shooting model-predictive control with the simulator as the model: per env ``num_samples`` candidate
+    action sequences of ``horizon`` steps, drawn U(-1, 1) from a torch generator seeded with ``seed``, are tried on
+    copies of the env in one call (``VecPushEnv.simulate_plans``) and ranked -- by the planning-mode PushReward of the
+    simulated states (``score_plans``, discount ``gamma``; ``use_plan_reward=True``) or by the discounted sum of the
+    rewards the env itself gave along the way.  The action is the first one of the best sequence, the lowest index
+    among equals; the env does not change.  ``env``: a ``VecPushEnv`` or a ``PushEnv``."""
+
+    def __init__(self, env, num_samples, horizon, gamma=1.0, seed=0, use_plan_reward=True, is_high_level=False, config=None):
+        super(ShootingPushPolicy, self).__init__(env, config)
+        if int(num_samples) < 1 or int(horizon) < 1:
+            raise ValueError('ShootingPushPolicy: num_samples and horizon must be positive')
+        self._vec = getattr(env, '_vec', env)      # (a PushEnv is a VecPushEnv of one)
+        self._single = self._vec is not env
+        self.num_samples, self.horizon, self.gamma = int(num_samples), int(horizon), float(gamma)
+        self.use_plan_reward, self.is_high_level = bool(use_plan_reward), bool(is_high_level)
+        self._torch = self._vec.world.torch
+        self._gen = self._torch.Generator(device=self._vec.device)
+        self.reseed(seed)
+        self.last_best = self.last_returns = None
+
+    def reseed(self, seed):
+        """start the candidate stream over: the same seed gives the same candidates again"""
+        self._gen.manual_seed(int(seed))
+
+    def plan(self, observation=None):
+        """(actions [N] + action shape, best int32 [N]) -- for a PushEnv one action and an int.  Also kept:
+        ``last_best`` and ``last_returns`` [N, S]."""
+        t, v = self._torch, self._vec
+        shape = (v.num_envs, self.num_samples, self.horizon) + tuple(v.action_shape)
+        cand = t.rand(shape, generator=self._gen, device=v.device, dtype=t.float32) * 2.0 - 1.0
+        states, rewards, _ = v.simulate_plans(cand)
+        if self.use_plan_reward:
+            returns, _, best = v.score_plans(states, None, self.is_high_level, self.gamma)
+        else:
+            disc = t.full((self.horizon,), self.gamma, device=v.device, dtype=t.float32) ** t.arange(self.horizon, device=v.device)
+            returns = (rewards * disc).sum(dim=2)
+            best = returns.argmax(dim=1).to(t.int32)      # (the first of equal maxima)
+        self.last_best, self.last_returns = best, returns
+        actions = cand[t.arange(v.num_envs, device=v.device), best.long(), 0]
+        if self._single:
+            return actions[0].cpu().numpy(), int(best[0])
+        return actions, best
+
+    def _action(self, observation):
+        return self.plan(observation)[0]
