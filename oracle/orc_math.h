@@ -57,13 +57,20 @@ static inline void v3cross(real* o, const real* a, const real* b) {
 }
 static inline real v3len(const real* a) { return rsqrt_(v3dot(a, a)); }
 
-/* own sincos / atan2 (cephes-style polynomials) for the float build */
+/* own sincos / atan2 (cephes-style polynomials) for the float build.
+ * Contract of the float build: |x| <= ORC_SINCOS_MAX (1e4), see sincosr in rv_dev_math.h; an angle that comes from
+ * outside (the grasp yaw of an action) goes through rsincos_arg first -- in both builds, so that they see one action. */
+#define ORC_SINCOS_MAX R(1.0e4)
+static inline real rsincos_arg(real x) { return rclamp(x, -ORC_SINCOS_MAX, ORC_SINCOS_MAX); }
 static inline void rsincos(real x, real* s, real* c) {
 #ifdef ORC_DOUBLE
   *s = sin(x); *c = cos(x);
 #else
   float k = rintf(x * 0.636619772367581343f);
-  float r = ((x - k * 1.5703125f) - k * 4.837512969970703125e-4f) - k * 7.54978995489188216e-8f;
+  float t = (x - k * 1.5703125f) - k * 4.837512969970703125e-4f;
+  float r = t - k * 7.54978995489188216e-8f;
+  /* next to a zero of sin or cos: the last step again with exact products and the fourth term (rv_dev_math.h) */
+  if (fabsf(r) < 1.52587890625e-5f) r = rfma(-k, -1.7151245100058819e-15f, rfma(-k, 7.54978995489188216e-8f, t));
   float z = r * r;
   float sp = r + r * z * (-1.6666654611e-1f + z * (8.3321608736e-3f + z * -1.9515295891e-4f));
   float cp = 1.0f - 0.5f * z + z * z * (4.166664568298827e-2f + z * (-1.388731625493765e-3f + z * 2.443315711809948e-5f));
@@ -163,11 +170,19 @@ static inline real quat_yaw(const real* q) {
 }
 
 /* static-xyz Euler angles of a unit quaternion (transformations.py:1034-1085
- * euler_from_matrix, axes 'sxyz', on the matrix of q): roll, pitch, yaw */
+ * euler_from_matrix, axes 'sxyz', on the matrix of q): roll, pitch, yaw.
+ * Gimbal-lock threshold: the double build keeps the reference-sized 1e-6; the float build uses 3e-4 ~ sqrt(eps_float)
+ * like the device (RV_EULER_LOCK_EPS in rv_dev_math.h, where the reason is written down): the matrix entries carry
+ * ~1e-7 of cancellation noise in float, so below cy ~ 1e-4 the regular branch returns noise for roll and yaw. */
+#ifdef ORC_DOUBLE
+#define ORC_EULER_LOCK_EPS 1e-6
+#else
+#define ORC_EULER_LOCK_EPS 3e-4f
+#endif
 static inline void quat_to_euler(const real* q, real* e) {
   real m[9]; qmat(m, q);
   real cy = rsqrt_(m[0] * m[0] + m[3] * m[3]);
-  if (cy > R(1e-6)) {
+  if (cy > ORC_EULER_LOCK_EPS) {
     e[0] = ratan2(m[7], m[8]);
     e[1] = ratan2(-m[6], cy);
     e[2] = ratan2(m[3], m[0]);
@@ -206,6 +221,7 @@ static inline uint32_t rng_u32(orc_rng* g) {
   return g->buf[g->idx++];
 }
 static inline real rng_uniform01(orc_rng* g) { return (real)(rng_u32(g) >> 8) * R(5.9604644775390625e-8); }
+/* (can return hi itself by rounding: see rv_dev_math.h) */
 static inline real rng_uniform(orc_rng* g, real lo, real hi) { return lo + (hi - lo) * rng_uniform01(g); }
 static inline int rng_randint(orc_rng* g, int n) { return (int)(rng_u32(g) % (uint32_t)n); }
 

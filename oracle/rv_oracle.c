@@ -2247,7 +2247,7 @@ static void execute_grasp(const orc_world* w, orc_env* e) {
   const rv_config* c = &w->cfg;
   real start[7];
   start[0] = e->action[0][0]; start[1] = e->action[0][1]; start[2] = e->action[0][2] + (real)c->finger_tip_offset;
-  euler_to_quat(start + 3, R(0.0), w->pose_f32 ? (real)(float)ORC_PI : ORC_PI, w->pose_f32 ? (real)(float)e->action[0][3] : e->action[0][3]);
+  euler_to_quat(start + 3, R(0.0), w->pose_f32 ? (real)(float)ORC_PI : ORC_PI, rsincos_arg(w->pose_f32 ? (real)(float)e->action[0][3] : e->action[0][3]));
   e->is_safe = 1; e->is_effective = 1;
   e->phase = RV_GPHASE_INITIAL; e->num_action_steps = 0;
   while (e->phase != RV_GPHASE_DONE) {

@@ -5064,7 +5064,7 @@ RV_DEV void genv_step_begin(Shared& S, const Consts& K, int zero_counters, int c
       e.obs_num_steps = e.num_steps; e.obs_num_episodes = e.num_episodes;
       // start = Pose([[x, y, z + FINGER_TIP_OFFSET], [0, pi, angle]])
       s.gstart[0] = e.action[0][0]; s.gstart[1] = e.action[0][1]; s.gstart[2] = e.action[0][2] + c->finger_tip_offset;
-      stq(s.gstart + 3, euler_to_quat(0.0f, RV_PI, e.action[0][3]));
+      stq(s.gstart + 3, euler_to_quat(0.0f, RV_PI, sincos_arg(e.action[0][3])));
       e.is_safe = 1; e.is_effective = 1;
       e.phase = RV_GPHASE_INITIAL; e.num_action_steps = 0;
     }
@@ -5106,7 +5106,7 @@ RV_DEV int genv_pstep_begin(Shared& S, const Consts& K) {
     if (lane == 0) {
       DevEnv& e = S.e; Scratch& s = S.s; const rv_config* c = K.cfg;
       s.gstart[0] = e.action[0][0]; s.gstart[1] = e.action[0][1]; s.gstart[2] = e.action[0][2] + c->finger_tip_offset;
-      stq(s.gstart + 3, euler_to_quat(0.0f, RV_PI, e.action[0][3]));
+      stq(s.gstart + 3, euler_to_quat(0.0f, RV_PI, sincos_arg(e.action[0][3])));
       s.wus_resume = stage == 1;
     }
   RV_LANES_END

@@ -52,7 +52,8 @@ RV_DEV float fclamp_pm(float x, float b) {
   return fclampr(x, -b, b);
 #endif
 }
-// the ONE explicit fused multiply-add of the build (the row update of the impulse-space solvers): a single rounding,
+// the explicit fused multiply-add of the build (the row update of the impulse-space solvers; sincosr's reduction next to a
+// zero): a single rounding,
 // v_fma_f32 on the device, fmaf on the host emulator and in the oracle (rfma); everything else is -ffp-contract=off
 RV_DEV float rv_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 // sqrtf() lowers to the correctly rounded v_sqrt_f32 + fma fix-up sequence on
@@ -76,9 +77,27 @@ RV_DEV v3 cross(v3 a, v3 b) {
 }
 RV_DEV float len(v3 a) { return fsqrtr(dot(a, a)); }
 
+// sin and cos of x by a three-term Cody-Waite reduction to |r| <= pi/4 and two short polynomials.
+// CONTRACT: |x| <= RV_SINCOS_MAX (1e4).  There the absolute error is <= 2^-23 (measured 9.2e-8), and for |x| <= 26 the
+// error is <= 2 ulp of the true value (measured 1.54), next to the zeros of sin and cos too: pi/2 = C1 + C2 + C3 + C4
+// with k C1 and k C2 exact; where the reduced argument is below 2^-16 the three-term result -- k * C3 rounded, C3 short
+// of pi/2 - C1 - C2 by 1.7e-15 -- would be off by up to 13.8 ulp (the floats of 3 pi/2, 3 pi, 6 pi), so there the last
+// step is redone with two fused multiply-adds and C4.
+// Beyond the domain the reduction runs out of bits (9.6e-7 at 1e5), and once |x| 2/pi >= 2^31 the
+// conversion (int)k is undefined in C++: x86 gives INT_MIN (q = 0), v_cvt_i32_f32 saturates (q = 3) -- host and device
+// would disagree.  Every caller passes an angle that is bounded by construction (joint positions, atan2r results, the
+// samplers' ranges) except the grasp yaw of an action, which goes through sincos_arg first.
+#define RV_SINCOS_MAX 1.0e4f
+// an angle that comes from outside (an action), brought into sincosr's domain: unchanged inside it, clamped beyond
+// (a NaN stays a NaN)
+RV_DEV float sincos_arg(float x) { return fclampr(x, -RV_SINCOS_MAX, RV_SINCOS_MAX); }
 RV_DEV void sincosr(float x, float* s, float* c) {
   float k = frintr(x * 0.636619772367581343f);
-  float r = ((x - k * 1.5703125f) - k * 4.837512969970703125e-4f) - k * 7.54978995489188216e-8f;
+  float t = (x - k * 1.5703125f) - k * 4.837512969970703125e-4f;
+  float r = t - k * 7.54978995489188216e-8f;
+  // next to a zero of sin or cos the rounding of k * C3 and of C3 itself is all of r: redo the last step there with
+  // exact products and the fourth term (an r of 2^-16 and more keeps the bits it always had)
+  if (fabsr(r) < 1.52587890625e-5f) r = rv_fma(-k, -1.7151245100058819e-15f, rv_fma(-k, 7.54978995489188216e-8f, t));
   float z = r * r;
   float sp = r + r * z * (-1.6666654611e-1f + z * (8.3321608736e-3f + z * -1.9515295891e-4f));
   float cp = 1.0f - 0.5f * z + z * z * (4.166664568298827e-2f + z * (-1.388731625493765e-3f + z * 2.443315711809948e-5f));
@@ -191,11 +210,18 @@ RV_DEV float quat_yaw(q4 q) {
 }
 
 // static-xyz Euler angles of a unit quaternion (transformations.py euler_from_matrix,
-// axes 'sxyz', on the matrix of q): roll, pitch, yaw
+// axes 'sxyz', on the matrix of q): roll, pitch, yaw.
+// The gimbal-lock threshold is NOT the reference's: its 4 eps of float64 ("_EPS"-sized, 1e-6 here before) is meant for
+// a matrix whose entries carry 1e-16 of noise.  In float the entries m[0], m[3], m[7], m[8] are differences of products
+// with ~1e-7 of cancellation noise, so roll = atan2(m7, m8) and yaw = atan2(m3, m0) are wrong by ~4.6e-7 / cy: pure noise
+// for 1e-6 < cy < 1e-4 (rotation error up to 0.4 rad for a body lying on its side).  The lock branch (yaw := 0, roll from
+// the large entries) is wrong by ~5 cy.  The two meet near sqrt(eps_float) = 3.4e-4; with 3e-4 the rotation rebuilt from
+// the angles is within 1.2e-3 rad of q everywhere (measured; tests/test_math_primitives.py asserts 2e-3).
+#define RV_EULER_LOCK_EPS 3e-4f
 RV_DEV void quat_to_euler(q4 q, float* e) {
   m3 m = qmat(q);
   float cy = fsqrtr(m.m[0] * m.m[0] + m.m[3] * m.m[3]);
-  if (cy > 1e-6f) {
+  if (cy > RV_EULER_LOCK_EPS) {
     e[0] = atan2r(m.m[7], m.m[8]);
     e[1] = atan2r(-m.m[6], cy);
     e[2] = atan2r(m.m[3], m.m[0]);
@@ -234,6 +260,8 @@ RV_DEV uint32_t rng_u32(Rng& g) {
   return r;
 }
 RV_DEV float rng_uniform01(Rng& g) { return (float)(rng_u32(g) >> 8) * 5.9604644775390625e-8f; }
+// uniform in [lo, hi]: rng_uniform01 is < 1, but lo + (hi - lo) * u is rounded twice and CAN return hi itself (lo = 1,
+// hi = 2, u = 1 - 2^-24: the sum 2 - 2^-24 is a tie and rounds to 2).  Pinned by tests/test_math_primitives.py.
 RV_DEV float rng_uniform(Rng& g, float lo, float hi) { return lo + (hi - lo) * rng_uniform01(g); }
 RV_DEV int rng_randint(Rng& g, int n) { return (int)(rng_u32(g) % (uint32_t)n); }
 
