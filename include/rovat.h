@@ -413,8 +413,8 @@ typedef struct rv_antipodal_params {
   int32_t use_crop;                    /* 0: CROP = None (the whole image)                   */
   int32_t crop[4];                     /* CROP = [r0, c0, r1, c1]                            */
   float   min_dist_from_boundary;      /* MIN_DIST_FROM_BOUNDARY > max(WH, WW)               */
-  float   min_grasp_dist;              /* MIN_GRASP_DIST (unused: one grasp per env)          */
-  float   angle_dist_weight;           /* ANGLE_DIST_WEIGHT (unused: one grasp per env)       */
+  float   min_grasp_dist;              /* MIN_GRASP_DIST (rv_policy_antipodal_multi only)      */
+  float   angle_dist_weight;           /* ANGLE_DIST_WEIGHT (unused: _sample never passes it)  */
   int32_t depth_samples_per_grasp;     /* DEPTH_SAMPLES_PER_GRASP, must be 1                 */
   float   min_depth_offset;            /* MIN_DEPTH_OFFSET                                   */
   float   max_depth_offset;            /* MAX_DEPTH_OFFSET                                   */
@@ -435,6 +435,20 @@ typedef struct rv_antipodal_params {
  * A grasp world only; invalid parameters: RV_ERR_VALUE. */
 int  rv_policy_antipodal(rv_world* w, const float* d_depth, const rv_antipodal_params* h_params, int32_t macro_index,
                          float* d_image_grasps, float* d_actions4, int32_t* d_status);
+/* ---- sample(depth, camera, num_samples) (image_grasp_sampler.py:220-375): up to num_samples DISTINCT grasps per env in
+ *      one launch, the reference's walk (:303-375) over the same key order as rv_policy_antipodal: a pair is accepted
+ *      when it passes the per-candidate checks and min_k image_dist(candidate, accepted_k) > MIN_GRASP_DIST, as NumPy
+ *      evaluates it (a NaN distance accepts); the walk stops at num_samples grasps or after
+ *      min(MAX_REJECTION_SAMPLES, #valid) pairs.  The weight of the angle term is image_dist's default 1.0:
+ *      ANGLE_DIST_WEIGHT stays unused, as in the reference.  d_image_grasps [N][K][5], d_actions4 [N][K][4] (or NULL),
+ *      K = num_samples; d_count [N]: the grasps found; rows count..K-1 repeat row 0 (grasps[:, :] = grasp, :366).
+ *      Row 0 is the grasp of rv_policy_antipodal, depth included; row k draws its depth from Philox counter words
+ *      (0xffffffff, 0xffffffff - k).  d_status [N]: RV_AP_OK when count >= 1, else the codes above under their rules,
+ *      and then all K rows carry the env's rv_policy_random draw and its projection.  RV_ERR_VALUE: whatever
+ *      rv_policy_antipodal refuses, num_samples outside [1, RV_AP_MAX_SAMPLES], a NULL d_count. ---- */
+#define RV_AP_MAX_SAMPLES 64
+int  rv_policy_antipodal_multi(rv_world* w, const float* d_depth, const rv_antipodal_params* h_params, int32_t macro_index,
+                               int32_t num_samples, float* d_image_grasps, float* d_actions4, int32_t* d_count, int32_t* d_status);
 
 /* ---- planning-mode PushReward: get_reward_fn(task, layout, is_planning=True) (push_reward.py:272-374 with the
  *      planning branches :110-151 insertion_termination, :168-200 crossing_termination, :230-238 check_stride,

@@ -20,6 +20,7 @@ RV_MAXG = 4
 RV_MAXQ = 8
 RV_AP_MAX_RADIUS = 32
 RV_AP_MAX_EDGES = 4096
+RV_AP_MAX_SAMPLES = 64
 RV_AP_OK, RV_AP_NO_EDGES, RV_AP_NO_PAIRS, RV_AP_ALL_REJECTED, RV_AP_TOO_MANY_EDGES = 1, 0, -1, -2, -3
 
 
@@ -221,6 +222,14 @@ STATE_API = {
     'rv_state_load': (C.c_int, [C.c_void_p, C.c_void_p, i32, C.c_void_p]),
     'rv_branch': (C.c_int, [C.c_void_p, C.c_void_p, i32]),
     'rv_plan_simulate': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, i32, i32, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
+
+# rv_policy_antipodal_multi (include/rovat.h): world, d_depth, h_params, macro_index, num_samples, d_image_grasps,
+# d_actions4, d_count, d_status; lib.load() binds it from here
+ANTIPODAL_API = {
+    'rv_policy_antipodal_multi': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(rv_antipodal_params), i32, i32,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 

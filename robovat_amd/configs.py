@@ -208,8 +208,8 @@ ANTIPODAL_GRASP_4DOF_POLICY_CONFIG = {
                                               # the default camera (rows 187-224, cols 239-273 with the objects' size)
                                               # plus a margin (tests/test_antipodal_host.py checks it)
         'MIN_DIST_FROM_BOUNDARY': 6,          # > the depth window, and clear of the crop's edge
-        'MIN_GRASP_DIST': 2.5,                # (unused: one grasp per env)
-        'ANGLE_DIST_WEIGHT': 5.0,             # (unused: one grasp per env)
+        'MIN_GRASP_DIST': 2.5,                # (rv_policy_antipodal_multi only: one grasp has nothing to be close to)
+        'ANGLE_DIST_WEIGHT': 5.0,             # (unused, as in the reference: _sample calls image_dist with its default 1.0)
         'DEPTH_SAMPLES_PER_GRASP': 1,         # one grasp per env
         'MIN_DEPTH_OFFSET': 0.015,            # fingertips 1.5 cm below the top the camera sees ...
         'MAX_DEPTH_OFFSET': 0.03,             # ... to 3 cm: the graspables are 2.8-4 cm tall

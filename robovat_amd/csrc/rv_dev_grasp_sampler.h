@@ -1,4 +1,5 @@
-// rv_dev_grasp_sampler.h — AntipodalGrasp4DofPolicy on the device (rv_policy_antipodal).
+// rv_dev_grasp_sampler.h — AntipodalGrasp4DofPolicy on the device (rv_policy_antipodal) and the
+// sampler's sample(depth, camera, num_samples) for several grasps (rv_policy_antipodal_multi).
 //
 // Reference chain (StanfordVL/robovat):
 //   AntipodalGrasp4DofPolicy._action          robovat/policies/grasp_policy.py:62-75
@@ -41,9 +42,38 @@
 //            depth = (cd + MIN_DEPTH_OFFSET) + u ((cd + MAX_DEPTH_OFFSET) - (cd + MIN_DEPTH_OFFSET)),
 //            u one more Philox draw (a counter no pair key takes), 24 bits in [0, 1)                     :359-372
 //
+// Several grasps per env (rv_policy_antipodal_multi, k_policy_antipodal_multi): the reference's
+// sample(depth, camera, num_samples), :303-375.  Steps 1-8, the pair keys and the (key, pixel i, pixel j) order are the
+// ones above (the same device functions); what differs is the walk:
+//  * the valid pairs are walked in key order until K = num_samples are accepted or K_draws = min(MAX_REJECTION_SAMPLES,
+//    #valid) pairs have been consumed.  A pair is accepted when it passes step 8 and is not close to a grasp accepted
+//    before it: min_k d_k > MIN_GRASP_DIST with d_k = |c_new - c_k| + 1.0 * arccos(a_new . a_k / F), c the centres,
+//    a_new the candidate's unit axis, a_k = p2_k - p1_k NOT normalised and F = sqrt(sum_k |p2_k - p1_k|^2) over ALL
+//    grasps accepted so far (image_dist :79-103 calls np.linalg.norm on the whole array of axes, not row by row);
+//  * the weight of the angle term is image_dist's default alpha = 1.0: _sample never passes ANGLE_DIST_WEIGHT, which
+//    therefore stays unused here as there;
+//  * np.min propagates NaN and NaN <= MIN_GRASP_DIST is false, so a candidate whose quotient exceeds 1 in magnitude
+//    against ANY accepted grasp is accepted (an axis parallel to the single accepted one can give 1 + 1 ulp);
+//  * the arithmetic is NumPy's on the reference's arrays (ap_close): the accepted grasps are rows of a float32 array, so
+//    F and a_k / F are float32 (the sum of squares is a sum of small integers: exact below 2^24, where a float32 dot
+//    product of any summation order agrees); the candidate is float64 and so is everything after the quotient -- the
+//    two products and their sum (never fused), both square roots, arccos and the comparison with MIN_GRASP_DIST (the
+//    float32 the parameter struct holds);
+//  * accepted grasp k draws its depth from Philox counter words (RV_AP_DRAW_CTR, RV_AP_DRAW_CTR - k): grasp 0 is the
+//    grasp of rv_policy_antipodal, depth included.  Rows count..K-1 repeat row 0 (grasps[:, :] = grasp, :366);
+//  * status RV_AP_OK when count >= 1, else the codes and rules above, and all K rows carry the random draw.
+// Bounded work, whatever the walk's length: the valid pairs whose (key, q) falls in a window [lo, hi) are gathered
+// into an LDS buffer of RV_AP_SEL entries (the first window is everything, so its count is #valid; when that overflows
+// the window is sized for half a buffer from #valid -- the keys are uniform --, and halved again on overflow), sorted
+// there (bitonic: the gather order is not deterministic), checked against step 8 by all threads, and walked by wave 0,
+// 64 entries at a time: lane k holds accepted grasp k and tests the distance to it, a ballot gives the verdict.  The
+// next window opens only when the buffer runs out.  Passes over the E^2 pairs: 1 while #valid <= RV_AP_SEL, else about
+// 2 + K_draws / (RV_AP_SEL / 2).  The result equals the sequential walk exactly.
+//
 // Departures (also in INTEGRATION.md):
-//  * one grasp per env (num_samples = 1, what the policy asks for): MIN_GRASP_DIST / ANGLE_DIST_WEIGHT are
-//    accepted and unused; DEPTH_SAMPLES_PER_GRASP must be 1 (the reference raises IndexError otherwise);
+//  * rv_policy_antipodal returns one grasp per env (num_samples = 1, what the policy asks for) and reads neither
+//    MIN_GRASP_DIST nor ANGLE_DIST_WEIGHT; rv_policy_antipodal_multi returns up to RV_AP_MAX_SAMPLES = 64 and reads
+//    MIN_GRASP_DIST.  DEPTH_SAMPLES_PER_GRASP must be 1 (the reference raises IndexError otherwise);
 //  * MIN_DIST_FROM_BOUNDARY > max(WH, WW) >= 1 is required, so a depth window never leaves the image (where
 //    NumPy slicing would wrap or shrink);
 //  * more than RV_AP_MAX_EDGES edge pixels: status RV_AP_TOO_MANY_EDGES, never a silent truncation.
@@ -51,7 +81,8 @@
 // Memory: the two filter passes go through a per-env slice [2][Hc][Wc] of a lazily grown world scratch
 // buffer (pass 1 in the first half, the filtered crop in the second; the resize reuses the first half).
 // The edge list (pixel, 4 B) and normals (float2, 8 B) live in LDS: RV_AP_MAX_EDGES = 4096 -> 48 KiB per
-// workgroup, three workgroups per CU within gfx950's 160 KiB.
+// workgroup, three workgroups per CU within gfx950's 160 KiB; k_policy_antipodal_multi adds the 16 KiB selection
+// buffer: 64.3 KiB, two workgroups per CU.
 #pragma once
 #include "../../include/rovat.h"
 #include "rv_dev_math.h"
@@ -63,6 +94,7 @@ namespace rv {
 #define RV_AP_TPB 256
 #define RV_AP_WAVES (RV_AP_TPB / 64)
 #define RV_AP_DRAW_CTR 0xffffffffu   // counter word 0 of the depth draw: pair keys use pixel indices < 2^31
+#define RV_AP_SEL 2048               // k_policy_antipodal_multi: entries of the selection buffer (16 KiB of LDS)
 
 struct ApArgs {
   rv_antipodal_params p;
@@ -73,6 +105,8 @@ struct ApArgs {
   float* grasps;            // [N][5]
   float* actions4;          // [N][4] or null
   int32_t* status;          // [N]
+  int num_samples;          // k_policy_antipodal_multi: K; grasps [N][K][5], actions4 [N][K][4]
+  int32_t* count;           // k_policy_antipodal_multi: [N] accepted grasps
 };
 
 struct ApShared {
@@ -206,21 +240,15 @@ RV_DEV unsigned long long ap_wave_min64(unsigned long long v) {
 RV_DEV int ap_wave_sum(int v) { for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64); return v; }
 RV_DEV float ap_wave_max(float v) { for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64)); return v; }
 
-// One workgroup per env (steps 1-9 above, then the 4-DoF action or the random fallback).
-__global__ __launch_bounds__(RV_AP_TPB) void k_policy_antipodal(const rv::DevEnv* envs, int n, const rv_config* c, rv::ApArgs A) {
+// Steps 2-5 for one env, by all RV_AP_TPB threads of its workgroup: the filtered crop (left in bufB), its maximum,
+// the downsampled image, and the edge list with its normals in s.  Returns the number of edge pixels found (which may
+// exceed RV_AP_MAX_EDGES: only the first RV_AP_MAX_EDGES are stored).
+RV_DEV int ap_edge_list(rv::ApShared& s, const rv::ApArgs& A, const float* img, float* bufA, float* bufB, float* max_filtered) {
   using namespace rv;
-  __shared__ ApShared s;
-  const int i = (int)blockIdx.x; if (i >= n) return;
   const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const rv_antipodal_params& p = A.p;
-  const int H = A.H, W = A.W, r0 = A.r0, c0 = A.c0, Hc = A.Hc, Wc = A.Wc, Hd = A.Hd, Wd = A.Wd;
+  const int W = A.W, r0 = A.r0, c0 = A.c0, Hc = A.Hc, Wc = A.Wc, Hd = A.Hd, Wd = A.Wd;
   const int rate = p.downsample_rate, R = p.gauss_radius;
-  const float* img = A.depth + (size_t)i * H * W;
-  float* bufA = A.scratch + (size_t)i * 2 * Hc * Wc;
-  float* bufB = bufA + (size_t)Hc * Wc;
-  const uint32_t gid = (uint32_t)(c->env_id_offset + i);
-  const uint32_t word3 = (RV_STREAM_GRASP << 24) | ((uint32_t)A.macro_index & 0xffffffu);
-
   // 2. Gaussian filter, axis 0 (crop -> bufA), then axis 1 (bufA -> bufB); max of the filtered crop
   for (int t = tid; t < Hc * Wc; t += RV_AP_TPB) {
     const int r = t / Wc, col = t - r * Wc;
@@ -245,6 +273,7 @@ __global__ __launch_bounds__(RV_AP_TPB) void k_policy_antipodal(const rv::DevEnv
   __syncthreads();
   mx = s.redf[0];
   for (int k = 1; k < RV_AP_WAVES; ++k) mx = fmaxf(mx, s.redf[k]);
+  *max_filtered = mx;
 
   // 3. PIL BILINEAR resize: horizontal pass bufB -> bufA [Hc][Wd], vertical pass -> bufA + Hc * Wd [Hd][Wd]
   const float* down = bufB;
@@ -292,39 +321,86 @@ __global__ __launch_bounds__(RV_AP_TPB) void k_policy_antipodal(const rv::DevEnv
     n_edges += tot;
     __syncthreads();
   }
-  const int E = n_edges;
+  return n_edges;
+}
+// 6. w_max squared, as the reference's Camera.project_point computes it (float64, rounded half to even)
+RV_DEV long long ap_wmax2(const rv_antipodal_params& p, const float* K, float max_filtered) {
+  long long wmax2 = 0x7fffffffffffffffll;
+  if (p.gripper_width > 0.0f) {
+    const double D = (double)max_filtered + (double)p.min_depth_offset, fx = K[0], cx = K[2];
+    const double u2 = rint(((double)p.gripper_width * fx + D * cx) / D), u1 = rint((D * cx) / D);
+    const long long wp = (long long)fabs(u2 - u1);
+    wmax2 = wp * wp;
+  }
+  return wmax2;
+}
+// 6. is the ordered pair q = a * E + b of edge pixels valid (antipodal normals, 0 < distance < w_max)?
+RV_DEV bool ap_pair_valid(const rv::ApShared& s, const rv_antipodal_params& p, long long wmax2, int E, int q, uint32_t* ea_out, uint32_t* eb_out) {
+  const int a = q / E, b = q - a * E;
+  if (a == b) return false;
+  const float2 na = s.nrm[a], nb = s.nrm[b];
+  if (!(na.x * nb.x + na.y * nb.y < -p.cone_cos)) return false;
+  const uint32_t ea = s.pix[a], eb = s.pix[b];
+  const long long dr = (long long)(ea >> 16) - (long long)(eb >> 16), dc = (long long)(ea & 0xffffu) - (long long)(eb & 0xffffu);
+  const long long rate2 = (long long)p.downsample_rate * p.downsample_rate;
+  if (!(rate2 * (dr * dr + dc * dc) < wmax2)) return false;
+  *ea_out = ea; *eb_out = eb;
+  return true;
+}
+// 7. the composite sort key of a valid pair: (Philox key, q)
+RV_DEV unsigned long long ap_pair_comp(const rv_config* c, uint32_t gid, uint32_t word3, const rv::ApArgs& A, uint32_t ea, uint32_t eb, int q) {
+  const int rate = A.p.downsample_rate;
+  const uint32_t key = rv::ap_key(c, gid, word3, rv::ap_pix(ea, rate, A.r0, A.c0, A.W), rv::ap_pix(eb, rate, A.r0, A.c0, A.W));
+  return ((unsigned long long)key << 32) | (uint32_t)q;
+}
+// 9. the image grasp of the accepted pair q with depth draw number k (k = 0: the one grasp of rv_policy_antipodal)
+RV_DEV void ap_grasp_row(const rv::ApShared& s, const rv::ApArgs& A, const rv_config* c, uint32_t gid, uint32_t word3, const float* img,
+                         int E, int q, uint32_t k, float* g) {
+  using namespace rv;
+  const rv_antipodal_params& p = A.p;
+  const int rate = p.downsample_rate, a = q / E, b = q - a * E;
+  float cd = 0.0f;
+  ap_check(s, A, img, a, b, &cd);
+  const uint32_t ea = s.pix[a], eb = s.pix[b];
+  g[0] = (float)(A.c0 + rate * (int)(ea & 0xffffu)); g[1] = (float)(A.r0 + rate * (int)(ea >> 16));
+  g[2] = (float)(A.c0 + rate * (int)(eb & 0xffffu)); g[3] = (float)(A.r0 + rate * (int)(eb >> 16));
+  const float u = (float)(ap_key(c, gid, word3, RV_AP_DRAW_CTR, RV_AP_DRAW_CTR - k) >> 8) * 5.9604644775390625e-8f;
+  const float lo = cd + p.min_depth_offset, hi = cd + p.max_depth_offset;
+  g[4] = lo + u * (hi - lo);
+}
+
+// One workgroup per env (steps 1-9 above, then the 4-DoF action or the random fallback).
+__global__ __launch_bounds__(RV_AP_TPB) void k_policy_antipodal(const rv::DevEnv* envs, int n, const rv_config* c, rv::ApArgs A) {
+  using namespace rv;
+  __shared__ ApShared s;
+  const int i = (int)blockIdx.x; if (i >= n) return;
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const rv_antipodal_params& p = A.p;
+  const float* img = A.depth + (size_t)i * A.H * A.W;
+  float* bufA = A.scratch + (size_t)i * 2 * A.Hc * A.Wc;
+  float* bufB = bufA + (size_t)A.Hc * A.Wc;
+  const uint32_t gid = (uint32_t)(c->env_id_offset + i);
+  const uint32_t word3 = (RV_STREAM_GRASP << 24) | ((uint32_t)A.macro_index & 0xffffffu);
+
+  float mx;
+  const int E = ap_edge_list(s, A, img, bufA, bufB, &mx);
   int status = RV_AP_OK;
   unsigned long long best = ~0ull;
   if (E == 0) status = RV_AP_NO_EDGES;
   else if (E > RV_AP_MAX_EDGES) status = RV_AP_TOO_MANY_EDGES;
   else {
-    // 6. w_max as the reference's Camera.project_point computes it (float64, rounded half to even)
-    const float* K = envs[i].cam_intrinsics;
-    long long wmax2 = 0x7fffffffffffffffll;
-    if (p.gripper_width > 0.0f) {
-      const double D = (double)mx + (double)p.min_depth_offset, fx = K[0], cx = K[2];
-      const double u2 = rint(((double)p.gripper_width * fx + D * cx) / D), u1 = rint((D * cx) / D);
-      const long long wp = (long long)fabs(u2 - u1);
-      wmax2 = wp * wp;
-    }
-    const long long rate2 = (long long)rate * rate;
+    const long long wmax2 = ap_wmax2(p, envs[i].cam_intrinsics, mx);
     // 7. pass 1: #valid and the arg-min key over the valid pairs that pass step 8.  A lane checks a candidate only
     // when it beats the lane's own best so far.
     int n_valid = 0;
     const int total = E * E;
     for (int q = tid; q < total; q += RV_AP_TPB) {
-      const int a = q / E, b = q - a * E;
-      if (a == b) continue;
-      const float2 na = s.nrm[a], nb = s.nrm[b];
-      if (!(na.x * nb.x + na.y * nb.y < -p.cone_cos)) continue;
-      const uint32_t ea = s.pix[a], eb = s.pix[b];
-      const long long dr = (long long)(ea >> 16) - (long long)(eb >> 16), dc = (long long)(ea & 0xffffu) - (long long)(eb & 0xffffu);
-      if (!(rate2 * (dr * dr + dc * dc) < wmax2)) continue;
+      uint32_t ea, eb;
+      if (!ap_pair_valid(s, p, wmax2, E, q, &ea, &eb)) continue;
       ++n_valid;
-      const uint32_t key = ap_key(c, gid, word3, ap_pix(ea, rate, r0, c0, W), ap_pix(eb, rate, r0, c0, W));
-      const unsigned long long comp = ((unsigned long long)key << 32) | (uint32_t)q;
+      const unsigned long long comp = ap_pair_comp(c, gid, word3, A, ea, eb, q);
       float cd;
-      if (comp < best && ap_check(s, A, img, a, b, &cd)) best = comp;
+      if (comp < best && ap_check(s, A, img, q / E, q % E, &cd)) best = comp;
     }
     n_valid = ap_wave_sum(n_valid);
     best = ap_wave_min64(best);
@@ -339,15 +415,9 @@ __global__ __launch_bounds__(RV_AP_TPB) void k_policy_antipodal(const rv::DevEnv
       // pass 2: valid pairs ranked before the choice
       int before = 0;
       for (int q = tid; q < total; q += RV_AP_TPB) {
-        const int a = q / E, b = q - a * E;
-        if (a == b) continue;
-        const float2 na = s.nrm[a], nb = s.nrm[b];
-        if (!(na.x * nb.x + na.y * nb.y < -p.cone_cos)) continue;
-        const uint32_t ea = s.pix[a], eb = s.pix[b];
-        const long long dr = (long long)(ea >> 16) - (long long)(eb >> 16), dc = (long long)(ea & 0xffffu) - (long long)(eb & 0xffffu);
-        if (!(rate2 * (dr * dr + dc * dc) < wmax2)) continue;
-        const uint32_t key = ap_key(c, gid, word3, ap_pix(ea, rate, r0, c0, W), ap_pix(eb, rate, r0, c0, W));
-        before += (((unsigned long long)key << 32) | (uint32_t)q) < best;
+        uint32_t ea, eb;
+        if (!ap_pair_valid(s, p, wmax2, E, q, &ea, &eb)) continue;
+        before += ap_pair_comp(c, gid, word3, A, ea, eb, q) < best;
       }
       before = ap_wave_sum(before);
       if (lane == 0) s.red32[wave] = before;
@@ -364,15 +434,7 @@ __global__ __launch_bounds__(RV_AP_TPB) void k_policy_antipodal(const rv::DevEnv
   const DevEnv& e = envs[i];
   float g[5], a4[4];
   if (status == RV_AP_OK) {
-    const int q = (int)(best & 0xffffffffu), a = q / E, b = q - a * E;
-    float cd = 0.0f;
-    ap_check(s, A, img, a, b, &cd);
-    const uint32_t ea = s.pix[a], eb = s.pix[b];
-    g[0] = (float)(c0 + rate * (int)(ea & 0xffffu)); g[1] = (float)(r0 + rate * (int)(ea >> 16));
-    g[2] = (float)(c0 + rate * (int)(eb & 0xffffu)); g[3] = (float)(r0 + rate * (int)(eb >> 16));
-    const float u = (float)(ap_key(c, gid, word3, RV_AP_DRAW_CTR, RV_AP_DRAW_CTR) >> 8) * 5.9604644775390625e-8f;
-    const float lo = cd + p.min_depth_offset, hi = cd + p.max_depth_offset;
-    g[4] = lo + u * (hi - lo);
+    ap_grasp_row(s, A, c, gid, word3, img, E, (int)(best & 0xffffffffu), 0u, g);
     ap_grasp_4dof(e.cam_intrinsics, e.cam_rotation, e.cam_translation, g, a4);
   } else {
     random_action(c, (int)gid, A.macro_index, a4);
@@ -381,4 +443,164 @@ __global__ __launch_bounds__(RV_AP_TPB) void k_policy_antipodal(const rv::DevEnv
   for (int k = 0; k < 5; ++k) A.grasps[(size_t)i * 5 + k] = g[k];
   if (A.actions4) for (int k = 0; k < 4; ++k) A.actions4[(size_t)i * 4 + k] = a4[k];
   A.status[i] = status;
+}
+
+// Is the candidate (cx1, cy1)-(cx2, cy2) close to the accepted grasp (x1, y1)-(x2, y2)?  image_dist (:79-103) as NumPy
+// evaluates it on the reference's arrays: the candidate is float64, the accepted grasps are rows of a float32 array, so
+// F = np.linalg.norm(all accepted axes) and the quotient axis / F are float32, everything after is float64.  sumsq is
+// sum_k |p2_k - p1_k|^2 over all accepted grasps (an exact integer).  *nan: the arccos argument is outside [-1, 1].
+RV_DEV bool ap_close(int cx1, int cy1, int cx2, int cy2, int x1, int y1, int x2, int y2, long long sumsq, double min_grasp_dist, bool* nan) {
+  const float F = sqrtf((float)sumsq);
+  const float ax = (float)(x2 - x1) / F, ay = (float)(y2 - y1) / F;
+  const double dx = (double)(cx2 - cx1), dy = (double)(cy2 - cy1);
+  const double len = sqrt(dx * dx + dy * dy);
+  const double ux = dx / len, uy = dy / len;
+  const double dot = ux * (double)ax + uy * (double)ay;
+  const double ex = 0.5 * (double)(cx1 + cx2) - 0.5 * (double)(x1 + x2), ey = 0.5 * (double)(cy1 + cy2) - 0.5 * (double)(y1 + y2);
+  const double pd = sqrt(ex * ex + ey * ey);
+  *nan = !(fabs(dot) <= 1.0);
+  return pd + 1.0 * acos(dot) <= min_grasp_dist;
+}
+
+struct ApSharedMulti {
+  rv::ApShared s;
+  unsigned long long sel[RV_AP_SEL];      // the valid pairs of the current key window: (key, q), bit 31 = passes step 8
+  int acc[RV_AP_MAX_SAMPLES];             // q of the accepted grasps, in walk order
+  int sel_count, n_acc;
+};
+
+// rv_policy_antipodal_multi: one workgroup per env, up to A.num_samples grasps (the walk described in the header comment).
+__global__ __launch_bounds__(RV_AP_TPB) void k_policy_antipodal_multi(const rv::DevEnv* envs, int n, const rv_config* c, rv::ApArgs A) {
+  using namespace rv;
+  __shared__ ApSharedMulti sm;
+  ApShared& s = sm.s;
+  const int i = (int)blockIdx.x; if (i >= n) return;
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const rv_antipodal_params& p = A.p;
+  const int K = A.num_samples, rate = p.downsample_rate;
+  const float* img = A.depth + (size_t)i * A.H * A.W;
+  float* bufA = A.scratch + (size_t)i * 2 * A.Hc * A.Wc;
+  float* bufB = bufA + (size_t)A.Hc * A.Wc;
+  const uint32_t gid = (uint32_t)(c->env_id_offset + i);
+  const uint32_t word3 = (RV_STREAM_GRASP << 24) | ((uint32_t)A.macro_index & 0xffffffu);
+
+  float mx;
+  const int E = ap_edge_list(s, A, img, bufA, bufB, &mx);
+  int status = RV_AP_ALL_REJECTED, n_acc = 0;
+  if (E == 0) status = RV_AP_NO_EDGES;
+  else if (E > RV_AP_MAX_EDGES) status = RV_AP_TOO_MANY_EDGES;
+  else {
+    const long long wmax2 = ap_wmax2(p, envs[i].cam_intrinsics, mx);
+    const int total = E * E;
+    const double mgd = (double)p.min_grasp_dist;
+    // the walk's state: every valid pair below lo has been walked (`consumed` of them); wave 0 keeps the accepted
+    // grasps in registers (lane k holds grasp k) and sum |axis|^2 over them
+    unsigned long long lo = 0ull, width = ~0ull;
+    int consumed = 0, n_valid = -1, K_draws = 0;
+    int my_x1 = 0, my_y1 = 0, my_x2 = 0, my_y2 = 0, my_q = 0;
+    long long sumsq = 0;
+    for (;;) {
+      // gather the valid pairs with lo <= (key, q) < hi; the first window is everything, so its count is #valid
+      unsigned long long hi;
+      int cnt;
+      for (;;) {
+        hi = width > ~0ull - lo ? ~0ull : lo + width;
+        if (tid == 0) sm.sel_count = 0;
+        __syncthreads();
+        for (int q = tid; q < total; q += RV_AP_TPB) {
+          uint32_t ea, eb;
+          if (!ap_pair_valid(s, p, wmax2, E, q, &ea, &eb)) continue;
+          const unsigned long long comp = ap_pair_comp(c, gid, word3, A, ea, eb, q);
+          if (comp < lo || comp >= hi) continue;
+          const int at = atomicAdd(&sm.sel_count, 1);
+          if (at < RV_AP_SEL) sm.sel[at] = comp;
+        }
+        __syncthreads();
+        cnt = sm.sel_count;
+        __syncthreads();
+        if (n_valid < 0) {
+          n_valid = cnt;
+          K_draws = n_valid < p.max_rejection_samples ? n_valid : p.max_rejection_samples;
+          // (the keys are uniform: a window this wide holds about half a buffer)
+          if (cnt > RV_AP_SEL) { width = (~0ull / (unsigned long long)cnt) * (unsigned long long)(RV_AP_SEL / 2); continue; }
+        }
+        if (cnt <= RV_AP_SEL) break;
+        width >>= 1;      // (cnt > RV_AP_SEL distinct values in the window: width > RV_AP_SEL)
+      }
+      if (n_valid == 0) { status = RV_AP_NO_PAIRS; break; }
+      // bitonic sort of the window (padded with ~0 to a power of two): the gather order is not deterministic
+      int m = 64; while (m < cnt) m <<= 1;
+      for (int t = cnt + tid; t < m; t += RV_AP_TPB) sm.sel[t] = ~0ull;
+      __syncthreads();
+      for (int k = 2; k <= m; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+          for (int t = tid; t < m; t += RV_AP_TPB) {
+            const int u = t ^ j;
+            if (u > t) {
+              const unsigned long long x = sm.sel[t], y = sm.sel[u];
+              if ((x > y) == ((t & k) == 0)) { sm.sel[t] = y; sm.sel[u] = x; }
+            }
+          }
+          __syncthreads();
+        }
+      // step 8 for the entries the walk may reach, all threads
+      const int limit = cnt < K_draws - consumed ? cnt : K_draws - consumed;
+      for (int t = tid; t < limit; t += RV_AP_TPB) {
+        const int q = (int)(sm.sel[t] & 0xffffffu);
+        float cd;
+        if (ap_check(s, A, img, q / E, q % E, &cd)) sm.sel[t] |= 0x80000000ull;
+      }
+      __syncthreads();
+      // the walk, wave 0: 64 entries at a time; for a passing entry lane k tests the distance to accepted grasp k
+      if (wave == 0) {
+        for (int base = 0; base < limit && n_acc < K; base += 64) {
+          const int t = base + lane;
+          unsigned long long pass = __ballot(t < limit && (sm.sel[t] & 0x80000000ull) != 0ull);
+          while (pass != 0ull && n_acc < K) {
+            const int r = __ffsll((long long)pass) - 1;
+            pass &= pass - 1ull;
+            const int q = (int)(sm.sel[base + r] & 0xffffffu);
+            const uint32_t ea = s.pix[q / E], eb = s.pix[q % E];
+            const int x1 = A.c0 + rate * (int)(ea & 0xffffu), y1 = A.r0 + rate * (int)(ea >> 16);
+            const int x2 = A.c0 + rate * (int)(eb & 0xffffu), y2 = A.r0 + rate * (int)(eb >> 16);
+            bool nan = false, close = false;
+            if (lane < n_acc) close = ap_close(x1, y1, x2, y2, my_x1, my_y1, my_x2, my_y2, sumsq, mgd, &nan);
+            // np.min propagates NaN and NaN <= MIN_GRASP_DIST is false: one NaN distance accepts the candidate
+            const bool any_nan = __ballot(nan) != 0ull, any_close = __ballot(close) != 0ull;
+            if (any_nan || !any_close) {
+              if (lane == n_acc) { my_x1 = x1; my_y1 = y1; my_x2 = x2; my_y2 = y2; my_q = q; }
+              sumsq += (long long)(x2 - x1) * (x2 - x1) + (long long)(y2 - y1) * (y2 - y1);
+              ++n_acc;
+            }
+          }
+        }
+        if (lane < n_acc) sm.acc[lane] = my_q;
+        if (lane == 0) sm.n_acc = n_acc;
+      }
+      __syncthreads();
+      n_acc = sm.n_acc;
+      consumed += cnt;
+      if (n_acc >= K || consumed >= K_draws || hi == ~0ull) break;
+      lo = hi;
+      if (cnt < RV_AP_SEL / 4 && width <= (~0ull >> 1)) width <<= 1;      // (a thin stretch of keys: do not crawl)
+    }
+    if (n_acc > 0) status = RV_AP_OK;
+  }
+
+  // 9. thread k writes row k: accepted grasp k, row 0 again past the count, or the random fallback in every row
+  if (tid == 0) { A.status[i] = status; A.count[i] = n_acc; }
+  if (tid >= K) return;
+  const DevEnv& e = envs[i];
+  float g[5], a4[4];
+  if (n_acc > 0) {
+    const int k = tid < n_acc ? tid : 0;
+    ap_grasp_row(s, A, c, gid, word3, img, E, sm.acc[k], (uint32_t)k, g);
+    ap_grasp_4dof(e.cam_intrinsics, e.cam_rotation, e.cam_translation, g, a4);
+  } else {
+    random_action(c, (int)gid, A.macro_index, a4);
+    ap_project(e.cam_intrinsics, e.cam_rotation, e.cam_translation, a4, g);
+  }
+  const size_t row = (size_t)i * K + tid;
+  for (int k = 0; k < 5; ++k) A.grasps[row * 5 + k] = g[k];
+  if (A.actions4) for (int k = 0; k < 4; ++k) A.actions4[row * 4 + k] = a4[k];
 }

@@ -1125,29 +1125,29 @@ int rv_render(rv_world* w, float* d_depth, uint8_t* d_segmask) {
   HIPCHK(hipGetLastError());
   return RV_OK;
 }
-int rv_policy_antipodal(rv_world* w, const float* d_depth, const rv_antipodal_params* h_params, int32_t macro_index,
-                        float* d_image_grasps, float* d_actions4, int32_t* d_status) {
-  WCHK(w); NEED(h_params, "rv_policy_antipodal"); NEED(d_image_grasps, "rv_policy_antipodal"); NEED(d_status, "rv_policy_antipodal");
+// the checks and the launch arguments the two antipodal entry points share (`fn`: the entry point the message names)
+static int antipodal_args(rv_world* w, const float* d_depth, const rv_antipodal_params* h_params, int32_t macro_index,
+                          const std::string& fn, ApArgs* out) {
   const rv_antipodal_params& p = *h_params;
-  if (w->cfg.env_type != RV_ENV_GRASP) return fail(RV_ERR_VALUE, "rv_policy_antipodal: a Grasp4DofEnv world only");
+  if (w->cfg.env_type != RV_ENV_GRASP) return fail(RV_ERR_VALUE, fn + ": a Grasp4DofEnv world only");
   const int H = w->cfg.cam_height, W = w->cfg.cam_width;
-  if (p.downsample_rate < 1 || p.downsample_rate > 8) return fail(RV_ERR_VALUE, "rv_policy_antipodal: DOWNSAMPLE_RATE must be an integer in 1..8");
-  if (p.depth_samples_per_grasp != 1) return fail(RV_ERR_VALUE, "rv_policy_antipodal: DEPTH_SAMPLES_PER_GRASP must be 1 (one grasp per env)");
-  if (p.max_rejection_samples < 1) return fail(RV_ERR_VALUE, "rv_policy_antipodal: MAX_REJECTION_SAMPLES must be positive");
-  if (p.gauss_radius < 0 || p.gauss_radius > RV_AP_MAX_RADIUS) return fail(RV_ERR_VALUE, "rv_policy_antipodal: Gaussian radius int(4 sigma + 0.5) outside [0, RV_AP_MAX_RADIUS]");
+  if (p.downsample_rate < 1 || p.downsample_rate > 8) return fail(RV_ERR_VALUE, fn + ": DOWNSAMPLE_RATE must be an integer in 1..8");
+  if (p.depth_samples_per_grasp != 1) return fail(RV_ERR_VALUE, fn + ": DEPTH_SAMPLES_PER_GRASP must be 1 (one depth per grasp)");
+  if (p.max_rejection_samples < 1) return fail(RV_ERR_VALUE, fn + ": MAX_REJECTION_SAMPLES must be positive");
+  if (p.gauss_radius < 0 || p.gauss_radius > RV_AP_MAX_RADIUS) return fail(RV_ERR_VALUE, fn + ": Gaussian radius int(4 sigma + 0.5) outside [0, RV_AP_MAX_RADIUS]");
   const float wh = p.depth_sample_window_height, ww = p.depth_sample_window_width;
   if (!(wh >= 1.0f && ww >= 1.0f && p.min_dist_from_boundary > (wh > ww ? wh : ww)))
-    return fail(RV_ERR_VALUE, "rv_policy_antipodal: need MIN_DIST_FROM_BOUNDARY > max(DEPTH_SAMPLE_WINDOW_HEIGHT, DEPTH_SAMPLE_WINDOW_WIDTH) >= 1");
-  if (!(p.cone_cos >= 0.0f && p.cone_cos <= 1.0f)) return fail(RV_ERR_VALUE, "rv_policy_antipodal: cone_cos = cos(arctan(FRICTION_COEF)) outside [0, 1]");
+    return fail(RV_ERR_VALUE, fn + ": need MIN_DIST_FROM_BOUNDARY > max(DEPTH_SAMPLE_WINDOW_HEIGHT, DEPTH_SAMPLE_WINDOW_WIDTH) >= 1");
+  if (!(p.cone_cos >= 0.0f && p.cone_cos <= 1.0f)) return fail(RV_ERR_VALUE, fn + ": cone_cos = cos(arctan(FRICTION_COEF)) outside [0, 1]");
   int r0 = 0, c0 = 0, r1 = H, c1 = W;
   if (p.use_crop) { r0 = p.crop[0]; c0 = p.crop[1]; r1 = p.crop[2]; c1 = p.crop[3]; }
-  if (!(0 <= r0 && r0 < r1 && r1 <= H && 0 <= c0 && c0 < c1 && c1 <= W)) return fail(RV_ERR_VALUE, "rv_policy_antipodal: CROP must be 0 <= r0 < r1 <= H, 0 <= c0 < c1 <= W");
+  if (!(0 <= r0 && r0 < r1 && r1 <= H && 0 <= c0 && c0 < c1 && c1 <= W)) return fail(RV_ERR_VALUE, fn + ": CROP must be 0 <= r0 < r1 <= H, 0 <= c0 < c1 <= W");
   ApArgs a;
   memset(&a, 0, sizeof(a));
   a.p = p; a.H = H; a.W = W; a.r0 = r0; a.c0 = c0; a.Hc = r1 - r0; a.Wc = c1 - c0;
   a.Hd = a.Hc / p.downsample_rate; a.Wd = a.Wc / p.downsample_rate;
-  if (a.Hd < 2 || a.Wd < 2) return fail(RV_ERR_VALUE, "rv_policy_antipodal: the downsampled crop must be at least 2 x 2");
-  a.macro_index = macro_index; a.grasps = d_image_grasps; a.actions4 = d_actions4; a.status = d_status;
+  if (a.Hd < 2 || a.Wd < 2) return fail(RV_ERR_VALUE, fn + ": the downsampled crop must be at least 2 x 2");
+  a.macro_index = macro_index;
   if (!d_depth) {
     int rc = ensure_floats(w, &w->d_ap_depth, &w->ap_depth_cap, (size_t)w->n * H * W); if (rc != RV_OK) return rc;
     rc = rv_render(w, w->d_ap_depth, nullptr); if (rc != RV_OK) return rc;
@@ -1155,7 +1155,28 @@ int rv_policy_antipodal(rv_world* w, const float* d_depth, const rv_antipodal_pa
   }
   int rc = ensure_floats(w, &w->d_ap_scratch, &w->ap_scratch_cap, (size_t)w->n * 2 * a.Hc * a.Wc); if (rc != RV_OK) return rc;
   a.depth = d_depth; a.scratch = w->d_ap_scratch;
+  *out = a;
+  return RV_OK;
+}
+int rv_policy_antipodal(rv_world* w, const float* d_depth, const rv_antipodal_params* h_params, int32_t macro_index,
+                        float* d_image_grasps, float* d_actions4, int32_t* d_status) {
+  WCHK(w); NEED(h_params, "rv_policy_antipodal"); NEED(d_image_grasps, "rv_policy_antipodal"); NEED(d_status, "rv_policy_antipodal");
+  ApArgs a;
+  int rc = antipodal_args(w, d_depth, h_params, macro_index, "rv_policy_antipodal", &a); if (rc != RV_OK) return rc;
+  a.grasps = d_image_grasps; a.actions4 = d_actions4; a.status = d_status;
   hipLaunchKernelGGL(k_policy_antipodal, dim3((unsigned)w->n), dim3(RV_AP_TPB), 0, w->stream, w->d_envs, w->n, w->d_cfg, a);
+  HIPCHK(hipGetLastError());
+  return RV_OK;
+}
+int rv_policy_antipodal_multi(rv_world* w, const float* d_depth, const rv_antipodal_params* h_params, int32_t macro_index,
+                              int32_t num_samples, float* d_image_grasps, float* d_actions4, int32_t* d_count, int32_t* d_status) {
+  WCHK(w); NEED(h_params, "rv_policy_antipodal_multi"); NEED(d_image_grasps, "rv_policy_antipodal_multi");
+  NEED(d_count, "rv_policy_antipodal_multi"); NEED(d_status, "rv_policy_antipodal_multi");
+  if (num_samples < 1 || num_samples > RV_AP_MAX_SAMPLES) return fail(RV_ERR_VALUE, "rv_policy_antipodal_multi: num_samples outside [1, RV_AP_MAX_SAMPLES]");
+  ApArgs a;
+  int rc = antipodal_args(w, d_depth, h_params, macro_index, "rv_policy_antipodal_multi", &a); if (rc != RV_OK) return rc;
+  a.grasps = d_image_grasps; a.actions4 = d_actions4; a.status = d_status; a.num_samples = num_samples; a.count = d_count;
+  hipLaunchKernelGGL(k_policy_antipodal_multi, dim3((unsigned)w->n), dim3(RV_AP_TPB), 0, w->stream, w->d_envs, w->n, w->d_cfg, a);
   HIPCHK(hipGetLastError());
   return RV_OK;
 }

@@ -43,6 +43,8 @@ class VecGrasp4DofEnv(object):
             raise ValueError('Unrecognized action type: %r' % (self.config.ACTION.TYPE,))
         self._macro_index = 0
         self.antipodal_status = self.antipodal_image_grasps = None
+        self.antipodal_count = self.antipodal_actions4 = None
+        self._plan_worlds = {}
 
     device = property(lambda s: s.world.device)
 
@@ -94,6 +96,69 @@ class VecGrasp4DofEnv(object):
         self.antipodal_status, self.antipodal_image_grasps = st, g
         return a if cuboid else g
 
+    def sample_antipodal_candidates(self, num_samples, depth=None, config=None):
+        """The reference sampler's ``sample(depth, camera, num_samples)`` on the device (rv_policy_antipodal_multi): up
+        to ``num_samples`` (K <= abi.RV_AP_MAX_SAMPLES) distinct antipodal grasps per env, in the env's ACTION.TYPE --
+        [N, K, 4] world actions for 'CUBOID', [N, K, 5] image grasps for 'IMAGE'.  Candidate 0 is the grasp
+        ``sample_antipodal_actions`` returns; ``antipodal_count`` [N] says how many an env found, the rows from there
+        on repeat candidate 0, and an env without any (``antipodal_status`` != 1) carries its RandomPolicy draw in all K
+        rows.  ``antipodal_status``, ``antipodal_count``, ``antipodal_image_grasps`` [N, K, 5] and
+        ``antipodal_actions4`` [N, K, 4] (the env's own calibration; what ``try_grasps`` takes) stay on the env."""
+        from robovat_amd import lib
+        g, a, cnt, st = self.world.policy_antipodal_multi(lib.antipodal_params(config), self._macro_index, num_samples,
+                                                          depth=depth, actions4=True)
+        self.antipodal_status, self.antipodal_count = st, cnt
+        self.antipodal_image_grasps, self.antipodal_actions4 = g, a
+        return a if self.config.ACTION.TYPE == 'CUBOID' else g
+
+    def save_state(self):
+        """All N envs as they are now (``lib.World.save_state``): a ``lib.Snapshot`` on the device, plus the index of the
+        env's next policy draw."""
+        snap = self.world.save_state()
+        snap.macro_index = self._macro_index
+        return snap
+
+    def restore_state(self, snap, mask=None):
+        """Put the envs back where ``snap`` was taken: all of them, or those flagged in ``mask`` (bool [N]; the others
+        keep their present state).  From then on they continue bit for bit as they did after the snapshot."""
+        if mask is None:
+            self.world.load_state(snap)
+            if getattr(snap, 'macro_index', None) is not None:
+                self._macro_index = snap.macro_index
+            return
+        torch = self.world.torch
+        m = torch.as_tensor(mask, device=self.device).reshape(self.num_envs).bool()
+        ar = torch.arange(self.num_envs, device=self.device, dtype=torch.int32)
+        self.world.load_state(snap, torch.where(m, ar, torch.full_like(ar, -1)))
+
+    def _plan_world(self, k):
+        """the world of N x K envs behind try_grasps: made on first use and kept per K; same scene, config and seed"""
+        w = self._plan_worlds.get(int(k))
+        if w is None:
+            from robovat_amd import lib
+            cfg = abi.rv_config.from_buffer_copy(bytes(self.rv_config))
+            cfg.n_envs = self.num_envs * int(k)
+            cfg.env_id_offset = int(self.rv_config.env_id_offset) * int(k)
+            w = self._plan_worlds[int(k)] = lib.World(cfg, self.scene, device=self.world.device_index)
+        return w
+
+    def try_grasps(self, actions4):
+        """Look ahead with the simulator: ``actions4`` [N, K, 4] are K candidate world actions [x, y, z, angle] per env
+        (``antipodal_actions4``).  Each is executed on a bit-exact copy of its env -- env j * K + k of a world of N x K
+        envs becomes env j (rv_branch) and takes one env.step() with candidate k -- and the envs themselves do not
+        change.  Returns (rewards float32 [N, K], dones uint8 [N, K]): what ``step`` would return for that action."""
+        torch = self.world.torch
+        a = torch.as_tensor(actions4, dtype=torch.float32, device=self.device)
+        if a.dim() != 3 or int(a.shape[0]) != self.num_envs or int(a.shape[1]) < 1 or int(a.shape[2]) != 4:
+            raise ValueError('try_grasps: actions4 must be [N, K, 4] with N = %d, got %s' % (self.num_envs, tuple(a.shape)))
+        k = int(a.shape[1])
+        w = self._plan_world(k)
+        w.branch_from(self.world, k)
+        w.set_actions(a.reshape(self.num_envs * k, 4))
+        w.step_macro()
+        r, d = w.reward()
+        return r.reshape(self.num_envs, k), d.reshape(self.num_envs, k)
+
     def contact_points(self, body_a=-1, link_a=-1, body_b=-1, link_b=-1, capacity=abi.RV_CP_MAX):
         """PyBullet contact records of every env on the device (``lib.World.contact_points``): ids [N, P, 4],
         data [N, P, RV_CP_NF], count [N]; bodies are slots, ``abi.RV_CP_TABLE`` or ``abi.RV_CP_ARM``."""
@@ -112,6 +177,9 @@ class VecGrasp4DofEnv(object):
         return self.world.stats()
 
     def close(self):
+        for w in self._plan_worlds.values():
+            w.close()
+        self._plan_worlds = {}
         self.world.close()
 
 
@@ -178,6 +246,33 @@ class Grasp4DofEnv(object):
         if status != 1:
             raise ValueError('Failed to sample any valid grasp (antipodal status %d).' % status)
         return a[0].cpu().numpy()
+
+    def sample_antipodal_candidates(self, num_samples, depth=None, config=None):
+        """Up to ``num_samples`` antipodal grasps for this env, [K, 4] or [K, 5] by ACTION.TYPE (rows past the number
+        found, ``antipodal_count``, repeat the first); ValueError when none is found."""
+        if depth is not None:
+            depth = np.asarray(depth, np.float32).reshape((1,) + np.shape(depth)[-2:])
+        a = self._vec.sample_antipodal_candidates(num_samples, depth, config)
+        status = int(self._vec.antipodal_status[0].item())
+        if status != 1:
+            raise ValueError('Failed to sample any valid grasp (antipodal status %d).' % status)
+        return a[0].cpu().numpy()
+
+    antipodal_status = property(lambda s: s._vec.antipodal_status)
+    antipodal_count = property(lambda s: s._vec.antipodal_count)
+    antipodal_image_grasps = property(lambda s: s._vec.antipodal_image_grasps)
+    antipodal_actions4 = property(lambda s: s._vec.antipodal_actions4)
+
+    def save_state(self):
+        return self._vec.save_state()
+
+    def restore_state(self, snap, mask=None):
+        self._vec.restore_state(snap, mask)
+
+    def try_grasps(self, actions4):
+        """``actions4`` [K, 4]: (rewards float32 [K], dones uint8 [K]) of each tried on a copy of this env."""
+        r, d = self._vec.try_grasps(np.asarray(actions4, np.float32).reshape(1, -1, 4))
+        return r[0].cpu().numpy(), d[0].cpu().numpy()
 
     def close(self):
         self._vec.close()

@@ -32,7 +32,7 @@ SYMBOLS = [
     'rv_reset_targets', 'rv_get_state_ptrs', 'rv_source_hash', 'rv_set_motor_targets', 'rv_grip',
     'rv_rollout_record', 'rv_render', 'rv_set_gravity', 'rv_rollout_record_full', 'rv_step_begin', 'rv_step_poll', 'rv_set_constraint', 'rv_render_rgb', 'rv_set_friction', 'rv_set_auto_reset',
     'rv_set_constraint_ex', 'rv_set_link_path', 'rv_get_robot_ready', 'rv_get_camera', 'rv_set_max_joint_velocities',
-    'rv_policy_antipodal', 'rv_get_contact_points', 'rv_env_kernel_build',
+    'rv_policy_antipodal', 'rv_policy_antipodal_multi', 'rv_get_contact_points', 'rv_env_kernel_build',
     'rv_plan_reward', 'rv_plan_score',
     'rv_state_bytes', 'rv_state_save', 'rv_state_load', 'rv_branch', 'rv_plan_simulate',
 ]
@@ -178,6 +178,9 @@ def load():
                  'rv_query_contacts', 'rv_get_manifold_counts', 'rv_get_episode_returns'):
         getattr(lib, name).argtypes = [vp, vp]
     abi.bind_state_api(lib)
+    for name, (res, args) in abi.ANTIPODAL_API.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = res, list(args)
     _lib = lib
     return lib
 
@@ -458,6 +461,24 @@ class World(object):
         check(self.lib.rv_policy_antipodal(self.h, None if d is None else self._ptr(d), C.byref(params), int(macro_index),
                                            self._ptr(g), None if a is None else self._ptr(a), self._ptr(st)))
         return g, a, st
+
+    def policy_antipodal_multi(self, params, macro_index, num_samples, depth=None, actions4=True):
+        """rv_policy_antipodal_multi: up to ``num_samples`` (K) distinct antipodal grasps for every env, the reference's
+        ``sample(depth, camera, K)``.  Arguments as ``policy_antipodal``.  Returns (image grasps [N, K, 5], 4-DoF
+        actions [N, K, 4] or None, count int32 [N], status int32 [N]); rows from ``count`` on repeat row 0, and row 0
+        is the grasp ``policy_antipodal`` returns."""
+        k = int(num_samples)
+        rows = min(max(k, 1), abi.RV_AP_MAX_SAMPLES)      # (the library refuses a K outside [1, RV_AP_MAX_SAMPLES])
+        g = self._new((self.n, rows, 5), self.torch.float32)
+        cnt = self._new((self.n,), self.torch.int32)
+        st = self._new((self.n,), self.torch.int32)
+        a = self._new((self.n, rows, 4), self.torch.float32) if actions4 else None
+        d = None
+        if depth is not None:
+            d = self._in(depth, (self.n, int(self.cfg.cam_height), int(self.cfg.cam_width)), self.torch.float32)
+        check(self.lib.rv_policy_antipodal_multi(self.h, None if d is None else self._ptr(d), C.byref(params), int(macro_index), k,
+                                                 self._ptr(g), None if a is None else self._ptr(a), self._ptr(cnt), self._ptr(st)))
+        return g, a, cnt, st
 
     def _plan_in(self, x, tail):
         """float32, contiguous, on the device and 16-byte aligned (the kernels read a [4][2] record as two float4);

@@ -57,6 +57,49 @@ class AntipodalGrasp4DofPolicy(Policy):
         raise NotImplementedError('AntipodalGrasp4DofPolicy needs a Grasp4DofEnv / VecGrasp4DofEnv')
 
 
+class LookaheadGrasp4DofPolicy(Policy):
+    """AntipodalGrasp4DofPolicy with one step of look-ahead, the simulator as the model: ``num_samples`` distinct
+    antipodal grasps per env (``sample_antipodal_candidates``, the reference sampler's ``sample(depth, camera, K)``) are
+    each tried on a bit-exact copy of the env (``try_grasps``), and the action is the lowest-index candidate whose
+    GraspReward is positive, else candidate 0 -- the grasp AntipodalGrasp4DofPolicy takes.  An env step is deterministic
+    given its action, so the env succeeds whenever one of its candidates does.  The action is in the env's ACTION.TYPE
+    (an 'IMAGE' env converts it with its nominal camera when it steps; the trial used the env's own calibration).
+    Kept: ``last_choice`` [N] and ``last_rewards`` [N, K].  ``env``: a ``VecGrasp4DofEnv`` or a ``Grasp4DofEnv``."""
+
+    def __init__(self, env, num_samples, config=None):
+        config = config or configs.AttrDict(configs.ANTIPODAL_GRASP_4DOF_POLICY_CONFIG)
+        super(LookaheadGrasp4DofPolicy, self).__init__(env, config)
+        self._vec = getattr(env, '_vec', env)      # (a Grasp4DofEnv is a VecGrasp4DofEnv of one)
+        self._single = self._vec is not env
+        if not hasattr(self._vec, 'try_grasps'):
+            raise NotImplementedError('LookaheadGrasp4DofPolicy needs a Grasp4DofEnv / VecGrasp4DofEnv')
+        self.num_samples = int(num_samples)
+        if self.num_samples < 1:
+            raise ValueError('LookaheadGrasp4DofPolicy: num_samples must be positive')
+        self.last_choice = self.last_rewards = None
+
+    def _action(self, observation):
+        v = self._vec
+        t = v.world.torch
+        depth = None if observation is None else observation.get('depth')
+        if depth is not None and self._single:
+            depth = np.asarray(depth, np.float32).reshape((1,) + np.shape(depth)[-2:])
+        cand = v.sample_antipodal_candidates(self.num_samples, depth, self.config)
+        if self._single and int(v.antipodal_status[0].item()) != 1:
+            raise ValueError('Failed to sample any valid grasp (antipodal status %d).' % int(v.antipodal_status[0].item()))
+        rewards, _ = v.try_grasps(v.antipodal_actions4)
+        k = self.num_samples
+        index = t.arange(k, device=v.device)[None, :].expand(v.num_envs, k)
+        first = t.where(rewards > 0, index, t.full_like(index, k)).min(dim=1).values      # (the lowest index that succeeds)
+        choice = t.where(first < k, first, t.zeros_like(first))
+        self.last_choice, self.last_rewards = choice, rewards
+        actions = cand[t.arange(v.num_envs, device=v.device), choice]
+        if self._single:
+            self.last_choice, self.last_rewards = int(choice[0]), rewards[0].cpu().numpy()
+            return actions[0].cpu().numpy()
+        return actions
+
+
 class ShootingPushPolicy(Policy):
     """Random-shooting model-predictive control with the simulator as the model: per env ``num_samples`` candidate
     action sequences of ``horizon`` steps, drawn U(-1, 1) from a torch generator seeded with ``seed``, are tried on
