@@ -1066,6 +1066,8 @@ RV_DEV void item_decode(const Shared& S, const Consts& K, const int owner, const
 // ONE solver row of a contact point (k = 0 the normal row, 1 / 2 the friction rows): everything the solvers
 // need of it.  row_setup() below is three calls of this; the lane-per-row solvers call it for their own row.
 struct RowK { v3 dir, rxa, rxb, aa, ab; float invk, vbc, target, mu, jf, cap; int fidx; };
+// (solve_singles holds a copy of the kind == 2 arithmetic below, written on operands it loaded up front -- DESIGN.md §10, "LDS
+// staging": a change here is made there too; tests/test_gpu_solver_entry.py case (d) and the parity sweep compare it with the oracle)
 RV_DEV void row_setup_k(const Shared& S, const Consts& K, int kind, int a, int b, const ManPoint& p, const int k, const int n_pts, RowK& o) {
   const rv_config* c = K.cfg; const DevEnv& e = S.e;
   float dt = c->dt;
@@ -1984,52 +1986,108 @@ RV_DEV void solve_singles(Shared& S, const Consts& K, const int smask, const int
             a2 = __builtin_amdgcn_readlane(na, 32), a3 = __builtin_amdgcn_readlane(na, 48);
   int namax = a0 > a1 ? a0 : a1; namax = namax > a2 ? namax : a2; namax = namax > a3 ? namax : a3;
   const bool arms = namax > 0;                             // (wave-uniform: some island of this solve has arm points)
-  // ---- this lane's table row: row_setup_k() for a body - table point, row k only
+  // ---- loads of BOTH row kinds first ("LDS staging"): b and p are always inside their arrays, the collider of an
+  // arm point that is not there is clamped to 0.  The chain of the arm row -- col[p] -> col_frame[col] -> the frame's pose and
+  // twist -- is on its way before the table row's arithmetic starts, not after it.
   J6 JT, PT, JA, PA;
   JT.l = JT.a = PT.l = PT.a = JA.l = JA.a = PA.l = PA.a = mk(0, 0, 0);
   float invkT = 0.0f, biasT = 0.0f, muT = 0.0f, lamT = 0.0f, gT = 0.0f;
   float invkA = 0.0f, biasA = 0.0f, muA = 0.0f, lamA = 0.0f, gA = 0.0f, capA = 0.0f;
+  const float dt = c->dt, erp = c->erp, slop = c->slop, max_pushout = c->max_pushout, warmstart = c->warmstart;
+  const float ground_friction = c->ground_friction, table_thickness = c->table_thickness, arm_friction = c->arm_friction;
+  const float finger_mass = c->finger_mass;
+  const int finger_dynamics = c->finger_dynamics, arm_effort_limit = c->arm_effort_limit;
+  const v3 posb = ld3(e.body[b]), velb = ld3(e.body[b] + 7), angb = ld3(e.body[b] + 10);
+  const m3 rotb = ldm(S.s.rot[b]), iia = ldm(S.s.iinv[b]);
+  const float ima = e.inv_mass[b], radius_b = e.radius[b], table_z = e.table_z, mu_table = e.mu_table, friction_b = e.friction[b];
+  const float mu_finger = e.mu_finger;
+  const v3 laT = ld3(mm.la[p]), d0T = ld3(mm.nrm[p]);
+  const float distT = mm.dist[p];
+  const float lnT = mm.ln[p], lt1T = mm.lt1[p], lt2T = mm.lt2[p];
+  v3 laA = mk(0, 0, 0), lbA = laA, d0A = laA, fposA = laA, fvA = laA, fwA = laA, fyA = laA;
+  m3 frotA = rotb;
+  float distA = 0.0f, lnA = 0.0f, lt1A = 0.0f, lt2A = 0.0f;
+  int colA = 0, man_n = 0;
+  if (arms) {
+    laA = ld3(ma.la[p]); lbA = ld3(ma.lb[p]); d0A = ld3(ma.nrm[p]); distA = ma.dist[p];
+    lnA = ma.ln[p]; lt1A = ma.lt1[p]; lt2A = ma.lt2[p];
+    man_n = ma.n;
+    const int col_raw = ma.col[p];
+    colA = actA ? col_raw : 0;
+    const int f = K.arm->col_frame[colA];
+    fposA = ld3(e.fpos[f]); fvA = ld3(S.s.fv[f]); fwA = ld3(S.s.fw[f]); frotA = ldm(S.s.frot[f]);
+    fyA = mk(S.s.frot[7][1], S.s.frot[7][4], S.s.frot[7][7]);
+  }
+  // ---- this lane's table row: row_setup_k() for a body - table point, row k only
   if (actT) {
-    const float dt = c->dt;
-    const v3 la = ld3(mm.la[p]), d0 = ld3(mm.nrm[p]);
-    const v3 wa = to_world_body(S, b, la);
-    const v3 ra = sub(wa, ld3(e.body[b]));
+    const v3 la = laT, d0 = d0T;
+    const v3 wa = add(posb, mulv(rotb, la));
+    const v3 ra = sub(wa, posb);
     v3 d1, d2;
     plane_space(d0, &d1, &d2);
     const v3 vb_pt = mk(0.0f, 0.0f, 0.0f);
-    const m3 iia = ldm(S.s.iinv[b]);
-    const float ima = e.inv_mass[b];
     const v3 dk = k == 0 ? d0 : (k == 1 ? d1 : d2);
     const v3 rxa = cross(ra, dk);
     const v3 aa = mulv(iia, rxa);
     const float kk = ima + dot(rxa, aa);
     invkT = 1.0f / kk;
     const float vbc = dot(dk, vb_pt);
-    const float dist = mm.dist[p];
+    const float dist = distT;
     float target;
     if (dist > 0.0f) target = -dist / dt;
-    else target = fminr(c->erp * fmaxr(-dist - c->slop, 0.0f) / dt, c->max_pushout);
-    const float mub = body_below_table(e, c, b) ? c->ground_friction : e.mu_table;
-    muT = e.friction[b] * mub;
+    else target = fminr(erp * fmaxr(-dist - slop, 0.0f) / dt, max_pushout);
+    const float mub = (posb.z + radius_b < table_z - table_thickness) ? ground_friction : mu_table;      // (body_below_table)
+    muT = friction_b * mub;
     biasT = k == 0 ? target : 0.0f;
     // (the impulses kept from the last substep, scaled as the row-setup phase scales them)
-    lamT = (k == 0 ? mm.ln[p] : (k == 1 ? mm.lt1[p] : mm.lt2[p])) * c->warmstart;
-    gT = dot(dk, ld3(e.body[b] + 7)) + dot(rxa, ld3(e.body[b] + 10));
+    lamT = (k == 0 ? lnT : (k == 1 ? lt1T : lt2T)) * warmstart;
+    gT = dot(dk, velb) + dot(rxa, angb);
     JT.l = dk; JT.a = rxa; PT.l = scale(dk, ima); PT.a = aa;
     gT -= vbc;
   }
   if (arms) {
     if (actA) {
-      // ... and its arm row (the pushed body): the arithmetic of the row-setup phase for an arm - body point
-      ManPoint pt;
-      pt.la = ld3(ma.la[p]); pt.lb = ld3(ma.lb[p]); pt.nrm = ld3(ma.nrm[p]); pt.dist = ma.dist[p]; pt.col = ma.col[p];
-      RowK o;
-      row_setup_k(S, K, 2, b, -1, pt, k, ma.n, o);
-      invkA = o.invk; muA = o.mu; biasA = k == 0 ? o.target : 0.0f; capA = o.cap;
-      lamA = (k == 0 ? ma.ln[p] : (k == 1 ? ma.lt1[p] : ma.lt2[p])) * c->warmstart;
-      gA = dot(o.dir, ld3(e.body[b] + 7)) + dot(o.rxa, ld3(e.body[b] + 10));
-      JA.l = o.dir; JA.a = o.rxa; PA.l = scale(o.dir, e.inv_mass[b]); PA.a = o.aa;
-      gA -= o.vbc;
+      // ... and its arm row (the pushed body): row_setup_k()'s arithmetic for an arm - body point, row k only, on the locals
+      const v3 wa = add(posb, mulv(rotb, laA));
+      const v3 wb = add(fposA, mulv(frotA, lbA));
+      const v3 ra = sub(wa, posb);
+      const v3 d0 = d0A;
+      v3 d1, d2;
+      plane_space(d0, &d1, &d2);
+      const v3 vb_pt = add(fvA, cross(fwA, sub(wb, fposA)));
+      const int fing = finger_dynamics && colA >= 8;
+      const v3 dk = k == 0 ? d0 : (k == 1 ? d1 : d2);
+      const v3 rxa = cross(ra, dk);
+      const v3 aa = mulv(iia, rxa);
+      float kk = ima + dot(rxa, aa);
+      if (fing) { const float jf = -dot(dk, fyA); kk += jf * jf / finger_mass; }
+      invkA = 1.0f / kk;
+      const float vbc = dot(dk, vb_pt);
+      // what the arm can push with along the normal (rv_config.arm_effort_limit, off by default: its loads stay here)
+      capA = 1e30f;
+      if (arm_effort_limit) {
+        const rv_arm* arm = K.arm;
+        const int f = arm->col_frame[colA];
+        const int fl = f < RV_NLIMB ? f : RV_NLIMB - 1;
+        float worst = 0.0f;
+#pragma unroll
+        for (int j = 0; j < RV_NLIMB; ++j) {
+          if (j > fl) continue;
+          const v3 lever = cross(ld3(S.s.axis[j]), sub(wb, ld3(e.fpos[j])));
+          worst = fmaxr(worst, fabsr(dot(lever, d0)) * arm->inv_tau_max[j]);
+        }
+        if (f >= 8 && !finger_dynamics) worst = fmaxr(worst, fabsr(dot(fyA, d0)) * arm->inv_tau_max[f - 1]);
+        if (worst > 0.0f) capA = dt / (worst * (float)man_n);
+      }
+      float target;
+      if (distA > 0.0f) target = -distA / dt;
+      else target = fminr(erp * fmaxr(-distA - slop, 0.0f) / dt, max_pushout);
+      muA = friction_b * (colA >= 8 ? mu_finger : arm_friction);
+      biasA = k == 0 ? target : 0.0f;
+      lamA = (k == 0 ? lnA : (k == 1 ? lt1A : lt2A)) * warmstart;
+      gA = dot(dk, velb) + dot(rxa, angb);
+      JA.l = dk; JA.a = rxa; PA.l = scale(dk, ima); PA.a = aa;
+      gA -= vbc;
     }
   }
   RV_PROF(25)
@@ -3898,31 +3956,90 @@ RV_DEV void sim_substep_heavy(Shared& S, const Consts& K) {
   // that hold points.  Every island stops on its own residual.  All rows of the env are
   // solved by the whole wave in impulse space, one lane per row (solve_rows above).
   int label[RV_MAXB], on_[RV_MAXB], act_[RV_NBB];
+  int on_mask = 0;
+#if RV_ON_DEVICE
+  // The awake / coupling state, read ONCE and lane-parallel: every lane loads the flags of body (lane & 3), of body pair
+  // min(lane, 5), of collider box min(lane, 9) and of arm point (lane >> 2) & 3 of its body -- loads first, stores last
+  // ("LDS staging") -- and ballots taken by the whole wave turn them into wave-uniform masks in SGPRs:
+  //   on_mask    bit b: body b is awake                       armn_mask  bit b: its arm manifold holds points
+  //   act_mask   bit k: pair k couples two awake bodies and holds points
+  //   con_mask   bit b: body b has a user constraint          unrest_m   = unrest_mask(S.e)
+  // Everything below is scalar arithmetic on these.  The contact flags and pairs_last -- what the row-setup phase computed
+  // on five lanes, one of them walking ten flags and four a data-dependent loop over dist[] -- come out of the same ballots.
+  int act_mask, armn_mask, con_mask, unrest_m, cfg_fingers, cfg_limb;
+  {
+    const int lane = (int)threadIdx.x;
+    DevEnv& e = S.e;
+    const int bl = lane & 3, il = (lane >> 2) & 3;
+    const int kl = lane < RV_NBB ? lane : RV_NBB - 1, cl = lane < RV_NCOL ? lane : RV_NCOL - 1;
+    const int l_act = e.active[bl], l_frz = e.frozen[bl], l_slp = e.asleep[bl];
+    const int l_con = e.con_on[bl], l_sc = e.sleep_count[bl];
+    const int l_an = e.man[RV_AIDX(bl)].n; const float l_ad = e.man[RV_AIDX(bl)].dist[il];
+    const int l_pn = e.man[RV_BBIDX(kl)].n;
+    const int l_cf = S.s.colflag[cl];
+    const int pr0 = S.s.pairs[0], pr1 = S.s.pairs[1], pr2 = S.s.pairs[2], pr3 = S.s.pairs[3], pl = e.pairs_last;
+    const float cqd = c->contact_query_dist;
+    const int l_fd = c->finger_dynamics, l_ld = c->limb_dynamics;
+    const int l_on = l_act && !l_frz && !l_slp;                                    // (body_on)
+    const unsigned m_on = (unsigned)__builtin_amdgcn_ballot_w64(l_on != 0);
+    const unsigned m_an = (unsigned)__builtin_amdgcn_ballot_w64(l_an > 0);
+    const unsigned m_con = (unsigned)__builtin_amdgcn_ballot_w64(l_con != 0);
+    const unsigned m_un = (unsigned)__builtin_amdgcn_ballot_w64(l_on && !(l_sc > 0));
+    const unsigned m_cf = (unsigned)__builtin_amdgcn_ballot_w64(lane < RV_NCOL && l_cf != 0);
+    const unsigned m_near = (unsigned)__builtin_amdgcn_ballot_w64(il < l_an && l_ad < cqd);   // lane 4 i + b, lanes 0 .. 15
+    on_mask = __builtin_amdgcn_readfirstlane((int)(m_on & 15u));
+    armn_mask = __builtin_amdgcn_readfirstlane((int)(m_an & 15u));
+    con_mask = __builtin_amdgcn_readfirstlane((int)(m_con & 15u));
+    unrest_m = __builtin_amdgcn_readfirstlane((int)(m_un & 15u));
+    const int both_l = (on_mask >> bb_a(kl)) & (on_mask >> bb_b(kl)) & 1;
+    act_mask = __builtin_amdgcn_readfirstlane((int)((unsigned)__builtin_amdgcn_ballot_w64(both_l && l_pn != 0) & ((1u << RV_NBB) - 1u)));
+    cfg_fingers = __builtin_amdgcn_readfirstlane(l_fd); cfg_limb = __builtin_amdgcn_readfirstlane(l_ld);
+    const unsigned near4 = (m_near | (m_near >> 4) | (m_near >> 8) | (m_near >> 12)) & 15u;
+    // ---- stores
+    if (lane < RV_MAXB) e.flag_arm_body[lane] = arm_on ? (int)((near4 >> lane) & 1u) : 0;
+    if (lane == 56) e.flag_arm_table = (arm_on && m_cf != 0u) ? 1 : 0;
+    if (lane == 61) e.pairs_last = pl + (pr0 + pr1 + pr2 + pr3);
+  }
+  RV_WAVE_SYNC();
+#pragma unroll
+  for (int b = 0; b < RV_MAXB; ++b) { label[b] = b; on_[b] = (on_mask >> b) & 1; }
+#pragma unroll
+  for (int k = 0; k < RV_NBB; ++k) act_[k] = (act_mask >> k) & 1;
+  // no awake body is coupled to another one, and the launch constants rule fingers, limb rows and constraints out: every
+  // awake body is an island of its own for solve_singles -- nothing of the island bookkeeping below is needed
+  const int uncoupled = act_mask == 0 && !cfg_fingers && !cfg_limb && (con_mask & on_mask) == 0;
+#else
 #pragma unroll
   for (int b = 0; b < RV_MAXB; ++b) { label[b] = b; on_[b] = body_on(S.e, b); }
-  int on_mask = 0;
 #pragma unroll
   for (int b = 0; b < RV_MAXB; ++b) on_mask |= on_[b] ? (1 << b) : 0;
 #pragma unroll
   for (int k = 0; k < RV_NBB; ++k) act_[k] = on_[bb_a(k)] && on_[bb_b(k)] && S.e.man[RV_BBIDX(k)].n != 0;
-#pragma unroll
-  for (int pass = 0; pass < RV_MAXB; ++pass)
-#pragma unroll
-    for (int k = 0; k < RV_NBB; ++k) {
-      const int a_ = bb_a(k), b_ = bb_b(k);
-      if (!act_[k]) continue;
-      const int lo = label[a_] < label[b_] ? label[a_] : label[b_];
-      label[a_] = lo; label[b_] = lo;
-    }
+  const int uncoupled = 0;
+#endif
   // members of every island; islands of one or two bodies go to the impulse-space solver
   int mem_[RV_MAXB], big_[RV_MAXB];
+  if (!uncoupled) {
 #pragma unroll
-  for (int b = 0; b < RV_MAXB; ++b) {
-    int m_ = 0;
+    for (int pass = 0; pass < RV_MAXB; ++pass)
 #pragma unroll
-    for (int x = 0; x < RV_MAXB; ++x) m_ += (on_[x] && label[x] == b);
-    mem_[b] = (on_[b] && label[b] == b) ? m_ : 0;
-    big_[b] = mem_[b] > 2;
+      for (int k = 0; k < RV_NBB; ++k) {
+        const int a_ = bb_a(k), b_ = bb_b(k);
+        if (!act_[k]) continue;
+        const int lo = label[a_] < label[b_] ? label[a_] : label[b_];
+        label[a_] = lo; label[b_] = lo;
+      }
+#pragma unroll
+    for (int b = 0; b < RV_MAXB; ++b) {
+      int m_ = 0;
+#pragma unroll
+      for (int x = 0; x < RV_MAXB; ++x) m_ += (on_[x] && label[x] == b);
+      mem_[b] = (on_[b] && label[b] == b) ? m_ : 0;
+      big_[b] = mem_[b] > 2;
+    }
+  } else {
+#pragma unroll
+    for (int b = 0; b < RV_MAXB; ++b) { mem_[b] = on_[b]; big_[b] = 0; }
   }
 #ifdef RV_EMU_COUNT
   { int n1 = 0, n2 = 0, n3 = 0; for (int b = 0; b < RV_MAXB; ++b) { n1 += mem_[b] == 1; n2 += mem_[b] == 2; n3 += mem_[b] > 2; }
@@ -3939,37 +4056,53 @@ RV_DEV void sim_substep_heavy(Shared& S, const Consts& K) {
     rv_emu_cnt[24] += arm_pts > 0; rv_emu_cnt[25] += (arm_pts == 0 && near); rv_emu_cnt[26] += (arm_pts == 0 && !near && S.s.arm_moving);
     rv_emu_cnt[27] += (arm_pts == 0 && !near && !S.s.arm_moving); rv_emu_cnt[28] += slow; rv_emu_cnt[29] += (slow && arm_pts == 0); }
 #endif
+#if RV_ON_DEVICE
+  const int with_fingers = cfg_fingers && arm_on;
+#else
   const int with_fingers = c->finger_dynamics && arm_on;
+#endif
   // force-limited gripper: at most one awake body (a grasp scene) -> impulse space with the two
   // finger DOFs and their motor rows, one lane per row; else the velocity-space system solver
   int n_on = 0, the_body = -1;
-#pragma unroll
-  for (int b = RV_MAXB - 1; b >= 0; --b) if (on_[b]) { ++n_on; the_body = b; }
   // an awake body with a user constraint: everything goes through the velocity-space system solver
   int any_con = 0;
-#pragma unroll
-  for (int b = 0; b < RV_MAXB; ++b) any_con |= on_[b] && S.e.con_on[b];
   // limb dynamics: an awake body touches the arm -> the joint velocities are unknowns too (system solver)
   int limb = 0;
-  if (c->limb_dynamics && arm_on) {
-#pragma unroll
-    for (int b = 0; b < RV_MAXB; ++b) limb |= on_[b] && S.e.man[RV_AIDX(b)].n > 0;
-  }
   // one awake body at most and no user constraint: impulse space, one lane per row, with the finger / limb
   // DOFs and their motor rows; else the velocity-space system solver
   // ... or several awake bodies of which ONE touches the arm and is an island by itself (the pushed body while
   // another one is still sliding on): the limb rows live in that island, the other islands of one or two bodies
   // are the usual independent problems
   int lone = 0;
-  if (limb) {
-    int n_arm = 0, lb = -1, any_big = 0;
+  if (!uncoupled) {     // (the uncoupled substep: no fingers, no limb rows, no constraint -- all of these stay 0)
 #pragma unroll
-    for (int b = RV_MAXB - 1; b >= 0; --b) { if (on_[b] && S.e.man[RV_AIDX(b)].n > 0) { ++n_arm; lb = b; } any_big |= big_[b]; }
-    int alone = 0;
+    for (int b = RV_MAXB - 1; b >= 0; --b) if (on_[b]) { ++n_on; the_body = b; }
+#if RV_ON_DEVICE
+    any_con = (on_mask & con_mask) != 0;
+    if (cfg_limb && arm_on) limb = (on_mask & armn_mask) != 0;
+#else
 #pragma unroll
-    for (int b = 0; b < RV_MAXB; ++b) if (b == lb) alone = mem_[b] == 1;
-    lone = n_arm == 1 && alone && !any_big && !with_fingers && n_on > 1;
-    if (lone) the_body = lb;
+    for (int b = 0; b < RV_MAXB; ++b) any_con |= on_[b] && S.e.con_on[b];
+    if (c->limb_dynamics && arm_on) {
+#pragma unroll
+      for (int b = 0; b < RV_MAXB; ++b) limb |= on_[b] && S.e.man[RV_AIDX(b)].n > 0;
+    }
+#endif
+    if (limb) {
+      int n_arm = 0, lb = -1, any_big = 0;
+#if RV_ON_DEVICE
+#pragma unroll
+      for (int b = RV_MAXB - 1; b >= 0; --b) { if (((on_mask & armn_mask) >> b) & 1) { ++n_arm; lb = b; } any_big |= big_[b]; }
+#else
+#pragma unroll
+      for (int b = RV_MAXB - 1; b >= 0; --b) { if (on_[b] && S.e.man[RV_AIDX(b)].n > 0) { ++n_arm; lb = b; } any_big |= big_[b]; }
+#endif
+      int alone = 0;
+#pragma unroll
+      for (int b = 0; b < RV_MAXB; ++b) if (b == lb) alone = mem_[b] == 1;
+      lone = n_arm == 1 && alone && !any_big && !with_fingers && n_on > 1;
+      if (lone) the_body = lb;
+    }
   }
   const int fing_fast = (with_fingers || limb) && !any_con && (n_on <= 1 || lone);
   // the other islands keep their lane-per-row solvers unless the one-lane system solver takes everything
@@ -3980,12 +4113,35 @@ RV_DEV void sim_substep_heavy(Shared& S, const Consts& K) {
   const int rows_all = ((with_fingers || limb) && !fing_fast) || (any_con && !limb);
   (void)rows_all;
 #if RV_ON_DEVICE
-  if (others_ok) {
+  if (uncoupled) smask = on_mask;
+  else if (others_ok) {
 #pragma unroll
     for (int b = 0; b < RV_MAXB; ++b) if (on_[b] && mem_[b] == 1 && !(lone && b == the_body)) smask |= 1 << b;     // (arm points or not)
     smask = __builtin_amdgcn_readfirstlane(smask);
   }
-#endif
+  // solver row setup (one lane per contact point).  The lane-per-row solvers (solve_singles, solve_island2) and the island of
+  // three or four bodies set their rows up themselves: only the one-lane system solver and the finger / limb solver want the
+  // kept impulses scaled here -- rows_all, false unless finger dynamics, limb dynamics or a user constraint is on.  (The
+  // contact flags and pairs_last: the mask phase above.)
+  if (rows_all) {
+  RV_LANES_BEGIN
+    DevEnv& e = S.e;
+    if (lane < RV_NMAN * 4) {
+      int mi = lane >> 2, i = lane & 3;
+      DevMan& m = e.man[mi];
+      int kind, a, b = -1;
+      if (mi < RV_MAXB) { kind = 0; a = mi; }
+      else if (mi < RV_MAXB + RV_NBB) { kind = 1; a = bb_a(mi - RV_MAXB); b = bb_b(mi - RV_MAXB); }
+      else { kind = 2; a = mi - RV_MAXB - RV_NBB; }
+      int use = body_on(e, a) && (kind != 1 || body_on(e, b));
+      if (use && i < m.n) {
+        const float ln = m.ln[i], lt1 = m.lt1[i], lt2 = m.lt2[i], ws = c->warmstart;
+        m.ln[i] = ln * ws; m.lt1[i] = lt1 * ws; m.lt2[i] = lt2 * ws;
+      }
+    }
+  RV_LANES_END
+  }
+#else
   // solver row setup (one lane per contact point) + contact flags
   RV_LANES_BEGIN
     DevEnv& e = S.e;
@@ -3997,27 +4153,13 @@ RV_DEV void sim_substep_heavy(Shared& S, const Consts& K) {
       else if (mi < RV_MAXB + RV_NBB) { kind = 1; a = bb_a(mi - RV_MAXB); b = bb_b(mi - RV_MAXB); }
       else { kind = 2; a = mi - RV_MAXB - RV_NBB; }
       int use = body_on(e, a) && (kind != 1 || body_on(e, b));
-#if RV_ON_DEVICE
-      // the lane-per-row solvers (solve_singles, solve_island2) set their rows up themselves; Row records are
-      // for the velocity-space paths only: an island of three or four bodies, the one-lane system solver
-      // (and, for now, the finger / limb solver)
-      {
-        int big_a = 0;
-#pragma unroll
-        for (int x = 0; x < RV_MAXB; ++x) if (x == a) big_a = big_[label[x]];
-        (void)big_a;
-        if (!rows_all) use = 0;
-      }
-#endif
       if (use && i < m.n) {
         ManPoint p;
         p.la = ld3(m.la[i]); p.lb = ld3(m.lb[i]); p.nrm = ld3(m.nrm[i]); p.dist = m.dist[i]; p.col = m.col[i];
         p.ln = m.ln[i]; p.lt1 = m.lt1[i]; p.lt2 = m.lt2[i];
-#if !RV_ON_DEVICE
         Row r;
         row_setup(S, K, kind, a, b, p, r, m.n);
         S.s.u.r.rows[mi][i] = r;
-#endif
         m.ln[i] = p.ln * c->warmstart; m.lt1[i] = p.lt1 * c->warmstart; m.lt2[i] = p.lt2 * c->warmstart;
       }
     } else if (lane == 61) {
@@ -4035,33 +4177,37 @@ RV_DEV void sim_substep_heavy(Shared& S, const Consts& K) {
       e.flag_arm_body[b] = f;
     }
   RV_LANES_END
+#endif
 
   RV_STOP(4)
   RV_PROF(4)
-  any_con |= limb;
-  if (limb) limb_prepare(S, K, fing_fast ? the_body : -1);
-  if (((with_fingers || limb) && !fing_fast) || (any_con && !limb)) {
+  if (!uncoupled) {
+    any_con |= limb;
+    if (limb) limb_prepare(S, K, fing_fast ? the_body : -1);
+    if (((with_fingers || limb) && !fing_fast) || (any_con && !limb)) {
 #if RV_ON_DEVICE
-    {
-      SerialRows SR;
-      serial_rows_setup(S, K, limb, SR);
-      RV_WAVE_SYNC();
-      solve_with_fingers(S, K, limb, SR);      // (every lane: see SerialRows)
-      RV_WAVE_SYNC();
-    }
+      {
+        SerialRows SR;
+        serial_rows_setup(S, K, limb, SR);
+        RV_WAVE_SYNC();
+        solve_with_fingers(S, K, limb, SR);      // (every lane: see SerialRows)
+        RV_WAVE_SYNC();
+      }
 #else
-    RV_LANES_BEGIN
-      if (lane == 0) solve_with_fingers(S, K, limb);
-    RV_LANES_END
+      RV_LANES_BEGIN
+        if (lane == 0) solve_with_fingers(S, K, limb);
+      RV_LANES_END
+#endif
+    }
+#if RV_ON_DEVICE
+    if (fing_fast) solve_island_fingers(S, K, __builtin_amdgcn_readfirstlane(the_body), with_fingers, limb);
 #endif
   }
 #if RV_ON_DEVICE
-  if (fing_fast) solve_island_fingers(S, K, __builtin_amdgcn_readfirstlane(the_body), with_fingers, limb);
-#endif
-#if RV_ON_DEVICE
-  {
-    // the partner / pair of every two-body island, then ONE instance of the island solver in
-    // the instruction stream, entered once per island of one or two bodies
+  // ONE instance of each island solver in the instruction stream: all islands of one body together, then the islands of two
+  if (smask) solve_singles(S, K, smask, unrest_m);
+  if (!uncoupled) {
+    // the partner / pair of every two-body island
     int isl_y[RV_MAXB], isl_k[RV_MAXB];
 #pragma unroll
     for (int b = 0; b < RV_MAXB; ++b) {
@@ -4073,8 +4219,6 @@ RV_DEV void sim_substep_heavy(Shared& S, const Consts& K) {
       for (int kk = 0; kk < RV_NBB; ++kk) if (bb_a(kk) == b && bb_b(kk) == y_) kxy = kk;
       isl_y[b] = mem_[b] == 2 ? y_ : -1; isl_k[b] = mem_[b] == 2 ? kxy : 0;
     }
-    const int unrest = __builtin_amdgcn_readfirstlane(unrest_mask(S.e));
-    if (smask) solve_singles(S, K, smask, unrest);
 #pragma nounroll
     for (int b = 0; b < RV_MAXB; ++b) {
       if ((smask >> b) & 1) continue;
@@ -4084,7 +4228,7 @@ RV_DEV void sim_substep_heavy(Shared& S, const Consts& K) {
       m_ = (!others_ok || (lone && b == the_body)) ? 0 : __builtin_amdgcn_readfirstlane(m_);
       if (m_ == 2) {       // (an island of one body is solve_singles')
         const int y1 = __builtin_amdgcn_readfirstlane(y_);
-        solve_island2(S, K, b, y1, __builtin_amdgcn_readfirstlane(kxy), tol_of(c, unrest & ((1 << b) | (1 << y1))));
+        solve_island2(S, K, b, y1, __builtin_amdgcn_readfirstlane(kxy), tol_of(c, unrest_m & ((1 << b) | (1 << y1))));
       }
     }
   }
@@ -4103,7 +4247,7 @@ RV_DEV void sim_substep_heavy(Shared& S, const Consts& K) {
   for (int b = RV_MAXB - 1; b >= 0; --b) if (big_[b]) big_root = b;
   RV_PROF(24)
 #if RV_ON_DEVICE
-  if (!with_fingers && !any_con && __builtin_amdgcn_readfirstlane(big_root) >= 0) {
+  if (!uncoupled && !with_fingers && !any_con && __builtin_amdgcn_readfirstlane(big_root) >= 0) {
     // Device: no Row records in LDS.  Lane 4 mi + i sets up the row set of point i of manifold mi in its
     // REGISTERS (row_setup(): what the row-setup phase computes) and scales the impulses kept from the last
     // substep; the body / pair lanes of the sweep below pull the row sets they visit out of those lanes with
@@ -4146,7 +4290,7 @@ RV_DEV void sim_substep_heavy(Shared& S, const Consts& K) {
     float big_best = 1e30f; int big_since = 0;        // rv_config.solver_stall
     float big_tol;                                     // the island's own tolerance (tol_of)
     {
-      const int unrest = __builtin_amdgcn_readfirstlane(unrest_mask(S.e));
+      const int unrest = unrest_m;
       int u_ = 0;
 #pragma unroll
       for (int x = 0; x < RV_MAXB; ++x) if (on_[x] && label[x] == root) u_ |= (unrest >> x) & 1;
