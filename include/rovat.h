@@ -514,6 +514,37 @@ int  rv_branch(rv_world* dst, rv_world* src, int32_t s);
 int  rv_plan_simulate(rv_world* plan, rv_world* src, const float* d_actions, int32_t s, int32_t h,
                       float* d_states, float* d_rewards, uint8_t* d_dones);
 
+/* ---- the two halves of a cross-entropy-method planner over rv_plan_simulate / rv_plan_score (no counterpart in the
+ *      reference): per env a normal distribution over plans of h steps, d_mean / d_std [N][D], D = h * G * 4 floats.
+ *      rv_cem_sample draws s candidates from it; rv_cem_refit fits it to the n_elites candidates with the largest
+ *      returns.  The arithmetic (logarithm, Box-Muller, ranking order, moments) is written out operation for operation
+ *      in csrc/rv_dev_cem.h.  A draw is Philox keyed by the world's seed, the GLOBAL env id, plan_index, iteration, the
+ *      params' seed, the candidate and the float's index -- not by N, s, h or by what else is in the world: shards,
+ *      partial batches and restored snapshots draw the same candidates.  Neither call reads more of an env than its
+ *      global id, and neither changes any env state.  Asynchronous on the world's stream.  RV_ERR_VALUE, with nothing
+ *      launched: s outside [1, RV_CEM_MAX_SAMPLES], h < 1, D > RV_CEM_MAX_DIM, plan_index outside [0, 2^24), iteration
+ *      outside [0, 2^15) (the key packing), a missing required pointer, a buffer that is not 4-byte aligned, a grasp
+ *      world; rv_cem_refit also: n_elites outside [1, s], alpha outside [0, 1), a negative or NaN min_std. ---- */
+#define RV_CEM_MAX_SAMPLES 1024
+#define RV_CEM_MAX_DIM 512
+typedef struct rv_cem_params {
+  int32_t plan_index, iteration;   /* Philox: the env.step() being planned, the CEM iteration */
+  uint32_t seed;                   /* the policy's seed, on top of the world's                */
+  int32_t keep_mean;               /* candidate 0 = the clamped mean                          */
+  int32_t n_elites;                /* E, rv_cem_refit only                                    */
+  float   alpha, min_std;          /* smoothing in [0,1), floor >= 0; rv_cem_refit only       */
+} rv_cem_params;
+/* d_actions [N][s][h][G][4] (the d_actions of rv_plan_simulate): fclamp(mean + std * z, -1, 1) with z standard normal,
+ * |z| <= 5.77; with keep_mean, candidate 0 is fclamp(mean, -1, 1). */
+int  rv_cem_sample(rv_world* w, const rv_cem_params* h_params, const float* d_mean, const float* d_std,
+                   int32_t s, int32_t h, float* d_actions);
+/* d_returns [N][s] ranks the candidates d_actions [N][s][h][G][4]: descending, the lower index first among equals, +-0
+ * equal, NaNs after every number and by index.  Over the first E = n_elites, per float d and in rank order: m = the
+ * mean, sd = the root of the mean squared deviation from m (ddof 0); then mean = alpha * mean + (1 - alpha) * m, std =
+ * max(alpha * std + (1 - alpha) * sd, min_std), in place.  d_elite [N][E]: the elites' indices by rank, or NULL. */
+int  rv_cem_refit(rv_world* w, const rv_cem_params* h_params, const float* d_actions, const float* d_returns,
+                  int32_t s, int32_t h, float* d_mean, float* d_std, int32_t* d_elite /* [N][E] or NULL */);
+
 /* ---- Simulator.step x n (simulator.py:94-103): ControllableBody.update +
  *      BulletPhysics.step (bullet_physics.py:106-109), no phase machine. ---- */
 int  rv_step_sub(rv_world* w, int32_t n_substeps);

@@ -214,6 +214,26 @@ class rv_plan_params(C.Structure):
     ]
 
 
+RV_CEM_MAX_SAMPLES = 1024
+RV_CEM_MAX_DIM = 512
+
+
+class rv_cem_params(C.Structure):
+    _fields_ = [
+        ('plan_index', i32), ('iteration', i32), ('seed', C.c_uint32), ('keep_mean', i32), ('n_elites', i32),
+        ('alpha', f32), ('min_std', f32),
+    ]
+
+
+# rv_cem_sample: world, h_params, d_mean, d_std, s, h, d_actions; rv_cem_refit: world, h_params, d_actions, d_returns, s, h,
+# d_mean, d_std, d_elite (include/rovat.h); lib.load() binds them from here
+CEM_API = {
+    'rv_cem_sample': (C.c_int, [C.c_void_p, C.POINTER(rv_cem_params), C.c_void_p, C.c_void_p, i32, i32, C.c_void_p]),
+    'rv_cem_refit': (C.c_int, [C.c_void_p, C.POINTER(rv_cem_params), C.c_void_p, C.c_void_p, i32, i32,
+                               C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
+
 # the env-state entry points of include/rovat.h (rv_state_* / rv_branch / rv_plan_simulate): name -> (restype, argtypes);
 # lib.load() binds them from here.  Worlds and device buffers are void pointers.
 STATE_API = {

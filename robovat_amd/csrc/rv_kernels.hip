@@ -6,6 +6,8 @@
 //                   substeps / settle loop out of LDS (rv_dev_env.h)
 //   k_contact_points one wave64 per env: the PyBullet contact records (rv_dev_contacts.h)
 //   k_plan_score    one workgroup per env, lanes over candidate plans: planning-mode PushReward (rv_dev_plan.h)
+//   k_cem_sample    one lane per four floats of a candidate plan: keyed normal draws (rv_dev_cem.h)
+//   k_cem_refit     one workgroup per env: rank the returns, refit mean / std to the elites (rv_dev_cem.h)
 //   k_*             small one-thread-per-env accessors behind the getters,
 //                   setters, observation, reward and policy entry points
 #include <hip/hip_runtime.h>
@@ -25,6 +27,7 @@
 #include "rv_dev_grasp_sampler.h"
 #include "rv_dev_contacts.h"
 #include "rv_dev_plan.h"
+#include "rv_dev_cem.h"
 
 using namespace rv;
 
@@ -1209,6 +1212,54 @@ int rv_plan_score(rv_world* w, const rv_plan_params* h_params, const float* d_st
   const int tpb = s <= 64 ? 64 : (s <= 256 ? 256 : RV_PLAN_MAX_TPB);
   const bool v4 = aligned_to(d_plans, 16);
   PLAN_DISPATCH(a.p.n_bodies, v4, launch_plan_score, w, a, tpb);
+  HIPCHK(hipGetLastError());
+  return RV_OK;
+}
+// the checks rv_cem_sample and rv_cem_refit share; *d = h * G * 4
+static int cem_check(const rv_world* w, const rv_cem_params* p, int32_t s, int32_t h, const std::string& me, int* d) {
+  if (!p) return fail(RV_ERR_VALUE, me + ": null params");
+  if (w->cfg.env_type == RV_ENV_GRASP) return fail(RV_ERR_VALUE, me + ": a PushEnv world only");
+  if (s < 1 || s > RV_CEM_MAX_SAMPLES) return fail(RV_ERR_VALUE, me + ": s outside [1, RV_CEM_MAX_SAMPLES]");
+  const int A = 4 * (w->cfg.num_goal_steps > 0 ? w->cfg.num_goal_steps : 1);
+  if (h < 1 || (long long)h * A > RV_CEM_MAX_DIM) return fail(RV_ERR_VALUE, me + ": h < 1 or h * G * 4 > RV_CEM_MAX_DIM");
+  if (p->plan_index < 0 || p->plan_index >= RV_CEM_MAX_PLAN_INDEX) return fail(RV_ERR_VALUE, me + ": plan_index outside [0, 2^24)");
+  if (p->iteration < 0 || p->iteration >= RV_CEM_MAX_ITERATION) return fail(RV_ERR_VALUE, me + ": iteration outside [0, 2^15)");
+  *d = h * A;
+  return RV_OK;
+}
+int rv_cem_sample(rv_world* w, const rv_cem_params* h_params, const float* d_mean, const float* d_std,
+                  int32_t s, int32_t h, float* d_actions) {
+  WCHK(w);
+  CemArgs a;
+  int rc = cem_check(w, h_params, s, h, "rv_cem_sample", &a.D); if (rc != RV_OK) return rc;
+  NEED(d_mean, "rv_cem_sample"); NEED(d_std, "rv_cem_sample"); NEED(d_actions, "rv_cem_sample");
+  if (!aligned_to(d_mean, 4) || !aligned_to(d_std, 4) || !aligned_to(d_actions, 4)) return fail(RV_ERR_VALUE, "rv_cem_sample: the buffers must be 4-byte aligned");
+  const long long total = (long long)w->n * s * (a.D / 4);      // one lane per four floats
+  if ((total + 255) / 256 > 0x7fffffffLL) return fail(RV_ERR_VALUE, "rv_cem_sample: too many candidates for one launch");
+  a.p = *h_params; a.actions = nullptr; a.returns = nullptr; a.elite = nullptr; a.S = s;
+  a.mean = const_cast<float*>(d_mean); a.std = const_cast<float*>(d_std); a.out = d_actions;
+  const dim3 grid((unsigned)((total + 255) / 256));
+  if (aligned_to(d_actions, 16)) hipLaunchKernelGGL(k_cem_sample<true>, grid, dim3(256), 0, w->stream, w->d_cfg, a, total);
+  else hipLaunchKernelGGL(k_cem_sample<false>, grid, dim3(256), 0, w->stream, w->d_cfg, a, total);
+  HIPCHK(hipGetLastError());
+  return RV_OK;
+}
+int rv_cem_refit(rv_world* w, const rv_cem_params* h_params, const float* d_actions, const float* d_returns,
+                 int32_t s, int32_t h, float* d_mean, float* d_std, int32_t* d_elite) {
+  WCHK(w);
+  CemArgs a;
+  int rc = cem_check(w, h_params, s, h, "rv_cem_refit", &a.D); if (rc != RV_OK) return rc;
+  if (h_params->n_elites < 1 || h_params->n_elites > s) return fail(RV_ERR_VALUE, "rv_cem_refit: n_elites outside [1, s]");
+  if (!(h_params->alpha >= 0.0f && h_params->alpha < 1.0f)) return fail(RV_ERR_VALUE, "rv_cem_refit: alpha outside [0, 1)");
+  if (!(h_params->min_std >= 0.0f)) return fail(RV_ERR_VALUE, "rv_cem_refit: min_std negative or NaN");
+  NEED(d_actions, "rv_cem_refit"); NEED(d_returns, "rv_cem_refit"); NEED(d_mean, "rv_cem_refit"); NEED(d_std, "rv_cem_refit");
+  if (!aligned_to(d_actions, 4) || !aligned_to(d_returns, 4) || !aligned_to(d_mean, 4) || !aligned_to(d_std, 4) || !aligned_to(d_elite, 4))
+    return fail(RV_ERR_VALUE, "rv_cem_refit: the buffers must be 4-byte aligned");
+  a.p = *h_params; a.actions = d_actions; a.returns = d_returns; a.mean = d_mean; a.std = d_std; a.out = nullptr;
+  a.elite = d_elite; a.S = s;
+  // one workgroup per env, k_plan_score's shapes
+  const int tpb = s <= 64 ? 64 : (s <= 256 ? 256 : RV_CEM_MAX_TPB);
+  hipLaunchKernelGGL(k_cem_refit, dim3((unsigned)w->n), dim3((unsigned)tpb), 0, w->stream, a);
   HIPCHK(hipGetLastError());
   return RV_OK;
 }

@@ -179,6 +179,35 @@ class VecPushEnv(object):
         st, r, d = self._plan_world(int(a.shape[1])).plan_simulate(self.world, a)
         return st, r, d.bool()
 
+    def sample_plan_candidates(self, mean, std, num_samples, iteration, seed=0, keep_mean=True):
+        """``num_samples`` candidate plans per env from the normal distribution ``mean`` / ``std`` ([N, H] + action
+        shape), clamped to the action space (``lib.World.cem_sample``).  A draw is keyed by the world's seed, the global
+        env id, the index of the env.step() being planned, ``iteration``, ``seed``, the candidate and the float: the
+        same whatever else is in the batch.  With ``keep_mean`` candidate 0 is the clamped mean.  Returns float32
+        [N, S, H] + action shape, the ``actions`` of ``simulate_plans``."""
+        from robovat_amd import lib
+        m = self.world.torch.as_tensor(mean)
+        if m.dim() != 2 + len(self.action_shape) or tuple(m.shape[2:]) != tuple(self.action_shape):
+            raise ValueError('sample_plan_candidates: mean and std must be [N, H] + %s' % (tuple(self.action_shape),))
+        h = int(m.shape[1])
+        p = lib.cem_params(plan_index=self._macro_index, iteration=int(iteration), seed=int(seed) & 0xFFFFFFFF, keep_mean=int(bool(keep_mean)))
+        a = self.world.cem_sample(m, std, p, int(num_samples), h)
+        return a.reshape((self.num_envs, int(a.shape[1]), h) + self.action_shape)
+
+    def refit_plan_distribution(self, candidates, returns, mean, std, num_elites, alpha=0.0, min_std=0.0):
+        """Fit ``mean`` / ``std`` ([N, H] + action shape) to the ``num_elites`` candidates ([N, S, H] + action shape) with
+        the largest ``returns`` [N, S] (``lib.World.cem_refit``): ranked descending, the lower index first among equals,
+        NaNs last; new = alpha * old + (1 - alpha) * (the elites' mean / standard deviation), the std not below
+        ``min_std``.  Returns (mean, std, elite int32 [N, E] by rank); the arguments stay as they are."""
+        from robovat_amd import lib
+        t = self.world.torch
+        c = t.as_tensor(candidates, dtype=t.float32, device=self.device)
+        if c.dim() != 3 + len(self.action_shape) or tuple(c.shape[3:]) != tuple(self.action_shape):
+            raise ValueError('refit_plan_distribution: candidates must be [N, S, H] + %s' % (tuple(self.action_shape),))
+        c = c.reshape(tuple(c.shape[:3]) + (self.world.G, 4))
+        p = lib.cem_params(plan_index=self._macro_index, n_elites=int(num_elites), alpha=float(alpha), min_std=float(min_std))
+        return self.world.cem_refit(c, returns, mean, std, p)
+
     def rollout(self, n_steps, auto_reset=True, record=True):
         before = self.world.env_counters().cpu().numpy()[:, [2, 4]] if (auto_reset and self._physics is not None) else None
         out = self.world.rollout(n_steps, self._macro_index, auto_reset, record)
@@ -326,6 +355,29 @@ class PushEnv(object):
             a = a[None]
         st, r, d = self._vec.simulate_plans(a)
         return st[0], r[0], d[0]
+
+    def sample_plan_candidates(self, mean, std, num_samples, iteration, seed=0, keep_mean=True):
+        """``VecPushEnv.sample_plan_candidates`` for this env: ``mean`` / ``std`` [H] + action shape (or with a leading
+        1).  Returns [S, H] + action shape."""
+        m, s = self._one(mean), self._one(std)
+        return self._vec.sample_plan_candidates(m, s, num_samples, iteration, seed, keep_mean)[0]
+
+    def refit_plan_distribution(self, candidates, returns, mean, std, num_elites, alpha=0.0, min_std=0.0):
+        """``VecPushEnv.refit_plan_distribution`` for this env: ``candidates`` [S, H] + action shape, ``returns`` [S],
+        ``mean`` / ``std`` [H] + action shape (or each with a leading 1).  Returns (mean, std, elite [E])."""
+        torch = self._vec.world.torch
+        c = torch.as_tensor(candidates)
+        if c.dim() == 2 + len(self._vec.action_shape):
+            c = c[None]
+        r = torch.as_tensor(returns)
+        r = r[None] if r.dim() == 1 else r
+        m, s, e = self._vec.refit_plan_distribution(c, r, self._one(mean), self._one(std), num_elites, alpha, min_std)
+        return m[0], s[0], e[0]
+
+    def _one(self, x):
+        """[H] + action shape -> [1, H] + action shape"""
+        x = self._vec.world.torch.as_tensor(x)
+        return x[None] if x.dim() == 1 + len(self._vec.action_shape) else x
 
     def close(self):
         self._vec.close()

@@ -35,6 +35,7 @@ SYMBOLS = [
     'rv_policy_antipodal', 'rv_policy_antipodal_multi', 'rv_get_contact_points', 'rv_env_kernel_build',
     'rv_plan_reward', 'rv_plan_score',
     'rv_state_bytes', 'rv_state_save', 'rv_state_load', 'rv_branch', 'rv_plan_simulate',
+    'rv_cem_sample', 'rv_cem_refit',
 ]
 
 _EXC = {abi.RV_ERR_VALUE: ValueError, abi.RV_ERR_STATE: RuntimeError,
@@ -178,9 +179,10 @@ def load():
                  'rv_query_contacts', 'rv_get_manifold_counts', 'rv_get_episode_returns'):
         getattr(lib, name).argtypes = [vp, vp]
     abi.bind_state_api(lib)
-    for name, (res, args) in abi.ANTIPODAL_API.items():
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = res, list(args)
+    for api in (abi.ANTIPODAL_API, abi.CEM_API):
+        for name, (res, args) in api.items():
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = res, list(args)
     _lib = lib
     return lib
 
@@ -237,6 +239,18 @@ def plan_params(**overrides):
     for k, v in overrides.items():
         if k not in names:
             raise TypeError('plan_params: unknown field %r' % (k,))
+        setattr(p, k, type(getattr(p, k))(v))
+    return p
+
+
+def cem_params(**overrides):
+    """An ``rv_cem_params``: plan_index 0, iteration 0, seed 0, keep_mean on, one elite, alpha 0 (no smoothing),
+    min_std 0.  Keyword arguments override fields."""
+    p = abi.rv_cem_params(plan_index=0, iteration=0, seed=0, keep_mean=1, n_elites=1, alpha=0.0, min_std=0.0)
+    names = [n for n, _ in abi.rv_cem_params._fields_]
+    for k, v in overrides.items():
+        if k not in names:
+            raise TypeError('cem_params: unknown field %r' % (k,))
         setattr(p, k, type(getattr(p, k))(v))
     return p
 
@@ -526,6 +540,54 @@ class World(object):
         check(self.lib.rv_plan_score(self.h, C.byref(p), None if s0 is None else self._ptr(s0), self._ptr(pl), s, h,
                                      self._ptr(ret), self._ptr(ln), self._ptr(best)))
         return ret, ln, best
+
+    # -- the cross-entropy-method planner's two kernels (include/rovat.h: rv_cem_sample / rv_cem_refit)
+    def _cem_dist(self, who, mean, std):
+        """mean and std as float32 [N, D] on the device, D from the tensors"""
+        m = self.torch.as_tensor(mean, dtype=self.torch.float32, device=self.device)
+        sd = self.torch.as_tensor(std, dtype=self.torch.float32, device=self.device)
+        if m.dim() < 2 or int(m.shape[0]) != self.n or tuple(sd.shape) != tuple(m.shape):
+            raise ValueError('%s: mean and std must both be [N, ...] with N = %d' % (who, self.n))
+        return m.reshape(self.n, -1).contiguous(), sd.reshape(self.n, -1).contiguous()
+
+    def cem_sample(self, mean, std, params, s, h):
+        """rv_cem_sample: ``s`` candidate plans of ``h`` steps per env from the normal distribution ``mean`` / ``std``
+        ([N, h * G * 4], or any [N, ...] of that many floats), clamped to [-1, 1].  ``params``: ``cem_params(...)``.
+        Returns float32 [N, s, h, G, 4], what ``plan_simulate`` takes."""
+        s, h = int(s), int(h)
+        m, sd = self._cem_dist('cem_sample', mean, std)
+        if int(m.shape[1]) != h * self.G * 4:
+            raise ValueError('cem_sample: mean and std must hold h * G * 4 = %d floats per env, got %d' % (h * self.G * 4, int(m.shape[1])))
+        rows = min(max(s, 1), abi.RV_CEM_MAX_SAMPLES)      # (the library refuses an s outside [1, RV_CEM_MAX_SAMPLES])
+        a = self._new((self.n, rows, max(h, 1), self.G, 4), self.torch.float32)
+        check(self.lib.rv_cem_sample(self.h, C.byref(params), self._ptr(m), self._ptr(sd), s, h, self._ptr(a)))
+        return a
+
+    def cem_refit(self, actions, returns, mean, std, params, elite=True):
+        """rv_cem_refit: rank the candidates ``actions`` [N, S, H, G, 4] by ``returns`` [N, S] and fit ``mean`` /
+        ``std`` ([N, H * G * 4], or any [N, ...] of that many floats) to the first ``params.n_elites``.  The arguments
+        stay as they are.  Returns (mean, std -- new tensors in the shape given --, elite int32 [N, E] by rank, or None
+        with ``elite=False``)."""
+        a = self.torch.as_tensor(actions, dtype=self.torch.float32, device=self.device)
+        if a.dim() == 4 and self.G == 1:
+            a = a[:, :, :, None]
+        if a.dim() != 5 or int(a.shape[0]) != self.n or tuple(a.shape[3:]) != (self.G, 4):
+            raise ValueError('cem_refit: actions must be [N, S, H, %d, 4] with N = %d, got %s' % (self.G, self.n, tuple(a.shape)))
+        s, h = int(a.shape[1]), int(a.shape[2])
+        r = self.torch.as_tensor(returns, dtype=self.torch.float32, device=self.device)
+        if tuple(r.shape) != (self.n, s):
+            raise ValueError('cem_refit: returns must be [N, S] = [%d, %d], got %s' % (self.n, s, tuple(r.shape)))
+        m, sd = self._cem_dist('cem_refit', mean, std)
+        if int(m.shape[1]) != h * self.G * 4:
+            raise ValueError('cem_refit: mean and std must hold H * G * 4 = %d floats per env, got %d' % (h * self.G * 4, int(m.shape[1])))
+        shape = tuple(self.torch.as_tensor(mean).shape)
+        m, sd = m.clone(), sd.clone()      # (the kernel updates in place)
+        a, r = a.contiguous(), r.contiguous()
+        e = int(params.n_elites)
+        el = self._new((self.n, min(max(e, 1), max(s, 1))), self.torch.int32) if elite else None
+        check(self.lib.rv_cem_refit(self.h, C.byref(params), self._ptr(a), self._ptr(r), s, h,
+                                    self._ptr(m), self._ptr(sd), None if el is None else self._ptr(el)))
+        return m.reshape(shape), sd.reshape(shape), el
 
     # -- env states as data (include/rovat.h: rv_state_* / rv_branch / rv_plan_simulate)
     def state_bytes(self):

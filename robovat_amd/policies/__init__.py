@@ -146,3 +146,96 @@ class ShootingPushPolicy(Policy):
 
     def _action(self, observation):
         return self.plan(observation)[0]
+
+
+class CEMPushPolicy(Policy):
+    """Cross-entropy-method model-predictive control with the simulator as the model.  Per env a normal distribution over
+    action sequences of ``horizon`` steps starts at mean 0, std ``init_std``; ``num_iterations`` times, ``num_samples``
+    candidates are drawn from it on the device (``VecPushEnv.sample_plan_candidates``: Philox keyed by the world's seed,
+    the global env id, the env.step() being planned, the iteration and ``seed`` -- an env plans the same whatever else is
+    in the batch), tried on copies of the env (``simulate_plans``), ranked as ``ShootingPushPolicy`` ranks them
+    (``score_plans`` with discount ``gamma``, or the discounted rewards the env gave), and the distribution is refit to
+    the ``num_elites`` best (default max(1, S // 8); ``refit_plan_distribution`` with smoothing ``alpha`` and the floor
+    ``min_std``).  With ``keep_mean`` candidate 0 of every iteration is the current mean.  The action is the first step
+    of the best-returning candidate seen in ANY iteration: the lowest iteration, then the lowest index among equals.
+    With ``warm_start`` the next call starts from this call's final mean shifted by one step (zeros in the last step, std
+    back to ``init_std``); ``reset(mask)`` forgets it for envs whose episode restarted.  The env does not change.
+    ``env``: a ``VecPushEnv`` or a ``PushEnv``."""
+
+    def __init__(self, env, num_samples, horizon, num_iterations=3, num_elites=None, gamma=1.0, init_std=0.5, min_std=0.05,
+                 alpha=0.0, seed=0, keep_mean=True, warm_start=True, use_plan_reward=True, is_high_level=False, config=None):
+        super(CEMPushPolicy, self).__init__(env, config)
+        if int(num_samples) < 1 or int(horizon) < 1 or int(num_iterations) < 1:
+            raise ValueError('CEMPushPolicy: num_samples, horizon and num_iterations must be positive')
+        self._vec = getattr(env, '_vec', env)      # (a PushEnv is a VecPushEnv of one)
+        self._single = self._vec is not env
+        self.num_samples, self.horizon, self.num_iterations = int(num_samples), int(horizon), int(num_iterations)
+        self.num_elites = max(1, self.num_samples // 8) if num_elites is None else int(num_elites)
+        if not 1 <= self.num_elites <= self.num_samples:
+            raise ValueError('CEMPushPolicy: num_elites must be in [1, num_samples]')
+        self.gamma, self.init_std, self.min_std, self.alpha = float(gamma), float(init_std), float(min_std), float(alpha)
+        self.seed, self.keep_mean, self.warm_start = int(seed), bool(keep_mean), bool(warm_start)
+        self.use_plan_reward, self.is_high_level = bool(use_plan_reward), bool(is_high_level)
+        self._torch = self._vec.world.torch
+        self._warm = None      # the next call's initial mean, [N, H] + action shape
+        self.last_mean = self.last_std = self.last_returns = self.last_best = None
+
+    def reset(self, mask=None):
+        """forget the warm start: of every env, or of those flagged in ``mask`` (bool [N]) -- their next plan starts at 0"""
+        if mask is None or self._warm is None:
+            self._warm = None
+            return
+        t = self._torch
+        m = t.as_tensor(mask, device=self._vec.device).reshape(self._vec.num_envs).bool()
+        self._warm = t.where(m.reshape((-1,) + (1,) * (self._warm.dim() - 1)), t.zeros_like(self._warm), self._warm)
+
+    def initial_mean(self):
+        """the mean the next ``plan()`` starts from, [N, H] + action shape"""
+        t, v = self._torch, self._vec
+        if self.warm_start and self._warm is not None:
+            return self._warm.clone()
+        return t.zeros((v.num_envs, self.horizon) + tuple(v.action_shape), dtype=t.float32, device=v.device)
+
+    def plan(self, observation=None):
+        """(actions [N] + action shape, (iteration int32 [N], index int32 [N]) of the chosen candidates) -- for a PushEnv
+        one action and two ints.  Also kept: ``last_mean`` / ``last_std`` [N, H] + action shape (the final distribution),
+        ``last_returns`` [I, N, S] and ``last_best`` (what is returned second)."""
+        t, v = self._torch, self._vec
+        n = v.num_envs
+        mean = self.initial_mean()
+        std = t.full_like(mean, self.init_std)
+        rows = t.arange(n, device=v.device)
+        all_returns = []
+        best_val = best_it = best_idx = best_act = None
+        for it in range(self.num_iterations):
+            cand = v.sample_plan_candidates(mean, std, self.num_samples, it, self.seed, self.keep_mean)
+            states, rewards, _ = v.simulate_plans(cand)
+            if self.use_plan_reward:
+                returns, _, best = v.score_plans(states, None, self.is_high_level, self.gamma)
+            else:
+                disc = t.full((self.horizon,), self.gamma, device=v.device, dtype=t.float32) ** t.arange(self.horizon, device=v.device)
+                returns = (rewards * disc).sum(dim=2)
+                best = returns.argmax(dim=1).to(t.int32)      # (the first of equal maxima)
+            val, act = returns[rows, best.long()], cand[rows, best.long(), 0]
+            if it == 0:
+                best_val, best_idx, best_act = val, best, act
+                best_it = t.zeros_like(best)
+            else:
+                better = val > best_val      # (strictly: the lowest iteration among equals)
+                best_val = t.where(better, val, best_val)
+                best_idx = t.where(better, best, best_idx)
+                best_it = t.where(better, t.full_like(best_it, it), best_it)
+                best_act = t.where(better.reshape((-1,) + (1,) * (act.dim() - 1)), act, best_act)
+            all_returns.append(returns)
+            mean, std, _ = v.refit_plan_distribution(cand, returns, mean, std, self.num_elites, self.alpha, self.min_std)
+        self.last_mean, self.last_std, self.last_returns = mean, std, t.stack(all_returns, dim=0)
+        self.last_best = (best_it, best_idx)
+        if self.warm_start:
+            self._warm = t.cat([mean[:, 1:], t.zeros_like(mean[:, :1])], dim=1)
+        if self._single:
+            self.last_best = (int(best_it[0]), int(best_idx[0]))
+            return best_act[0].cpu().numpy(), self.last_best
+        return best_act, self.last_best
+
+    def _action(self, observation):
+        return self.plan(observation)[0]

@@ -19,6 +19,7 @@
 #   variants       headline + configs 5 / 3 / 4 for the product library and every build/librovat_*.so
 #   sweep          tools/parity_sweep.py for both builds of the env kernel
 #   poison         pytest -m gpu with every build/librovat_poison_*.so (LDS scratch starts as garbage)
+#   cem            tools/cem_bench.py: the CEM planner's two kernels against torch, and the goal-rate comparison
 #   lanes          SQ_THREAD_CYCLES_VALU / SQ_ACTIVE_INST_VALU lane-utilisation pass (headline and no-deactivation)
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}; TAG=$1; shift
 O=$R/gpurun_out/$TAG; mkdir -p $O; cd $R
@@ -58,6 +59,9 @@ for STAGE in "$@"; do
     parts_c3)   timeout 600 python tools/prof_rollout.py --warm 0 --envs 4096 --steps 10 --top 6 --over TASK_NAME=crossing LAYOUT_ID=0 MOVABLE_NAME=CONCAVE MAX_STEPS=10 > $O/parts_c3.txt 2>&1; head -40 $O/parts_c3.txt ;;
     parts_c4)   timeout 600 python tools/prof_rollout.py --warm 0 --envs 2048 --steps 10 --top 6 --grasp > $O/parts_c4.txt 2>&1; head -40 $O/parts_c4.txt ;;
     parts_c5)   timeout 400 python tools/prof_rollout.py --warm 1 --envs 8192 --steps 10 --top 6 > $O/parts_c5.txt 2>&1; head -40 $O/parts_c5.txt ;;
+    cem)
+      timeout -k 10 900 python tools/cem_bench.py --out $O/cem_bench.txt > $O/cem_bench.log 2>&1; echo "cem rc=$?" >> $O/time.txt
+      tail -20 $O/cem_bench.txt ;;
     lanes)
       cd /tmp
       for V in head nd; do
