@@ -545,6 +545,32 @@ int  rv_cem_sample(rv_world* w, const rv_cem_params* h_params, const float* d_me
 int  rv_cem_refit(rv_world* w, const rv_cem_params* h_params, const float* d_actions, const float* d_returns,
                   int32_t s, int32_t h, float* d_mean, float* d_std, int32_t* d_elite /* [N][E] or NULL */);
 
+/* ---- the depth sensor noise model of the reference's perception/depth_utils.py (gamma_noise, gaussian_noise) on
+ *      [N][height][width] float buffers, N = the world's n_envs; both env kinds.  Per env: one multiplicative
+ *      Gamma(k, 1/k) sample g, k = gamma_shape (Marsaglia-Tsang); with probability prob a grid of N(0, sigma^2) values,
+ *      [height / R][width / R], upsampled x R by Pillow's bicubic resize and added where depth * g > 0.  The arithmetic is
+ *      written out operation for operation in csrc/rv_dev_depth_noise.h.  A draw is Philox keyed by the world's seed, the
+ *      GLOBAL env id, draw_index, the params' seed and the grid index -- not by N or by what else is in the world.  The
+ *      call reads no more of an env than its global id and changes no env state.  d_depth_out may be d_depth_in.  The
+ *      optional outputs record the draws: d_gamma [N], d_applied [N] (0 / 1), d_grid [N][height / R][width / R] (written
+ *      for envs with applied != 0 and sigma > 0 only; NULL: the world keeps a scratch grid of its own).  Asynchronous on
+ *      the world's stream.  RV_ERR_VALUE, with nothing launched: a missing required pointer, a buffer that is not 4-byte
+ *      aligned, height or width < 1, rescale_factor outside [1, 8] or not dividing height and width, draw_index outside
+ *      [0, 2^24), gamma_shape negative, NaN or in (0, 1), prob outside [0, 1] or NaN, sigma negative or NaN, more pixels
+ *      than one launch takes. ---- */
+typedef struct rv_depth_noise_params {
+  int32_t  height, width;      /* of the depth buffers                         */
+  int32_t  draw_index;         /* [0, 2^24): which observation of the env      */
+  uint32_t seed;               /* the caller's stream                          */
+  float    gamma_shape;        /* 0 = off, else >= 1                           */
+  float    prob;               /* [0, 1]                                       */
+  int32_t  rescale_factor;     /* R in [1, 8], divides height and width        */
+  float    sigma;              /* >= 0, 0 = off                                */
+} rv_depth_noise_params;
+int  rv_depth_noise(rv_world* w, const rv_depth_noise_params* h_params, const float* d_depth_in,
+                    float* d_depth_out /* may be d_depth_in */, float* d_gamma /* [N] or NULL */,
+                    uint8_t* d_applied /* [N] or NULL */, float* d_grid /* [N][H/R][W/R] or NULL */);
+
 /* ---- Simulator.step x n (simulator.py:94-103): ControllableBody.update +
  *      BulletPhysics.step (bullet_physics.py:106-109), no phase machine. ---- */
 int  rv_step_sub(rv_world* w, int32_t n_substeps);

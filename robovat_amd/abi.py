@@ -234,6 +234,25 @@ CEM_API = {
 }
 
 
+RV_DN_MAX_DRAW_INDEX = 1 << 24
+RV_DN_MAX_RESCALE = 8
+
+
+class rv_depth_noise_params(C.Structure):
+    _fields_ = [
+        ('height', i32), ('width', i32), ('draw_index', i32), ('seed', C.c_uint32), ('gamma_shape', f32), ('prob', f32),
+        ('rescale_factor', i32), ('sigma', f32),
+    ]
+
+
+# rv_depth_noise: world, h_params, d_depth_in, d_depth_out, d_gamma, d_applied, d_grid (include/rovat.h); lib.load() binds
+# it from here
+DEPTH_NOISE_API = {
+    'rv_depth_noise': (C.c_int, [C.c_void_p, C.POINTER(rv_depth_noise_params), C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p]),
+}
+
+
 # the env-state entry points of include/rovat.h (rv_state_* / rv_branch / rv_plan_simulate): name -> (restype, argtypes);
 # lib.load() binds them from here.  Worlds and device buffers are void pointers.
 STATE_API = {

@@ -167,7 +167,10 @@ def _grasp_env_config():
         'FRICTION_DESCEND': [0.001, 100.0], 'FRICTION_LIFT': [100.0, 1.0],
     }
     cfg['MIN_MOVABLE_BODIES'] = cfg['MAX_MOVABLE_BODIES'] = 1
-    cfg['OBSERVATION'] = {'TYPE': 'depth'}
+    # DEPTH_NOISE: None (clean depth images), or the sensor noise model of perception/depth_utils.py applied to every
+    # depth observation on the device: {'GAMMA_SHAPE': 1000, 'PROB': 0.5, 'RESCALE_FACTOR': 4, 'SIGMA': 0.005, 'SEED': 0}
+    # (rv_depth_noise)
+    cfg['OBSERVATION'] = {'TYPE': 'depth', 'DEPTH_NOISE': None}
     cfg['PHYSICS'].update({'FINGER_DYNAMICS': True, 'FINGER_MASS': 0.1, 'FINGER_MAX_FORCE': 20.0})
     return cfg
 

@@ -8,6 +8,8 @@
 //   k_plan_score    one workgroup per env, lanes over candidate plans: planning-mode PushReward (rv_dev_plan.h)
 //   k_cem_sample    one lane per four floats of a candidate plan: keyed normal draws (rv_dev_cem.h)
 //   k_cem_refit     one workgroup per env: rank the returns, refit mean / std to the elites (rv_dev_cem.h)
+//   k_depth_noise_draw / k_depth_noise_apply   the depth sensor noise model: keyed per-image scalars and noise grid, then
+//                   gamma multiplier + bicubic upsampling staged in LDS, one lane per pixel (rv_dev_depth_noise.h)
 //   k_*             small one-thread-per-env accessors behind the getters,
 //                   setters, observation, reward and policy entry points
 #include <hip/hip_runtime.h>
@@ -28,6 +30,7 @@
 #include "rv_dev_contacts.h"
 #include "rv_dev_plan.h"
 #include "rv_dev_cem.h"
+#include "rv_dev_depth_noise.h"
 
 using namespace rv;
 
@@ -580,6 +583,9 @@ struct rv_world {
   // rv_branch / rv_plan_simulate: FNV-1a of the rv_scene the world was made from (two worlds may exchange env blocks only
   // when they share it), and the event that orders a copy between the streams of two worlds
   uint64_t scene_hash; hipEvent_t ev_state;
+  // rv_depth_noise: [N] multipliers, [N] flags (as words), then the noise grid when the caller gives none (floats; grown
+  // on demand)
+  float* d_dn_scratch; size_t dn_scratch_cap;
 };
 
 static thread_local std::string g_err;
@@ -797,6 +803,7 @@ int rv_create(const rv_config* cfg, const rv_scene* scene, int device, rv_world*
   w->cfg = *cfg; w->device = device; w->n = cfg->n_envs; w->stream = nullptr; w->timed = false;
   w->d_snaps = nullptr; w->n_snaps_cap = 0;
   w->d_ap_depth = nullptr; w->ap_depth_cap = 0; w->d_ap_scratch = nullptr; w->ap_scratch_cap = 0;
+  w->d_dn_scratch = nullptr; w->dn_scratch_cap = 0;
   w->scene_hash = bytes_hash(scene, sizeof(rv_scene));
   {
     // one wave per env: with more envs than SIMDs the two-waves-per-SIMD build of the env kernel pays
@@ -842,6 +849,7 @@ int rv_destroy(rv_world* w) {
   if (w->d_snaps) (void)hipFree(w->d_snaps);
   if (w->d_ap_depth) (void)hipFree(w->d_ap_depth);
   if (w->d_ap_scratch) (void)hipFree(w->d_ap_scratch);
+  if (w->d_dn_scratch) (void)hipFree(w->d_dn_scratch);
   (void)hipEventDestroy(w->ev0); (void)hipEventDestroy(w->ev1); (void)hipEventDestroy(w->ev_state);
   delete w;
   return RV_OK;
@@ -1260,6 +1268,45 @@ int rv_cem_refit(rv_world* w, const rv_cem_params* h_params, const float* d_acti
   // one workgroup per env, k_plan_score's shapes
   const int tpb = s <= 64 ? 64 : (s <= 256 ? 256 : RV_CEM_MAX_TPB);
   hipLaunchKernelGGL(k_cem_refit, dim3((unsigned)w->n), dim3((unsigned)tpb), 0, w->stream, a);
+  HIPCHK(hipGetLastError());
+  return RV_OK;
+}
+int rv_depth_noise(rv_world* w, const rv_depth_noise_params* h_params, const float* d_depth_in, float* d_depth_out,
+                   float* d_gamma, uint8_t* d_applied, float* d_grid) {
+  WCHK(w);
+  if (!h_params) return fail(RV_ERR_VALUE, "rv_depth_noise: null params");
+  NEED(d_depth_in, "rv_depth_noise"); NEED(d_depth_out, "rv_depth_noise");
+  const rv_depth_noise_params& p = *h_params;
+  if (!aligned_to(d_depth_in, 4) || !aligned_to(d_depth_out, 4) || !aligned_to(d_gamma, 4) || !aligned_to(d_grid, 4))
+    return fail(RV_ERR_VALUE, "rv_depth_noise: the buffers must be 4-byte aligned");
+  if (p.height < 1 || p.width < 1) return fail(RV_ERR_VALUE, "rv_depth_noise: height or width < 1");
+  const int R = p.rescale_factor;
+  if (R < 1 || R > RV_DN_MAX_RESCALE) return fail(RV_ERR_VALUE, "rv_depth_noise: rescale_factor outside [1, 8]");
+  if (p.height % R != 0 || p.width % R != 0) return fail(RV_ERR_VALUE, "rv_depth_noise: rescale_factor must divide height and width");
+  if (p.draw_index < 0 || p.draw_index >= RV_DN_MAX_DRAW_INDEX) return fail(RV_ERR_VALUE, "rv_depth_noise: draw_index outside [0, 2^24)");
+  if (!(p.gamma_shape == 0.0f || p.gamma_shape >= 1.0f)) return fail(RV_ERR_VALUE, "rv_depth_noise: gamma_shape must be 0 (off) or >= 1");
+  if (!(p.prob >= 0.0f && p.prob <= 1.0f)) return fail(RV_ERR_VALUE, "rv_depth_noise: prob outside [0, 1]");
+  if (!(p.sigma >= 0.0f)) return fail(RV_ERR_VALUE, "rv_depth_noise: sigma negative or NaN");
+  DnArgs a;
+  a.p = p; a.in = d_depth_in; a.out = d_depth_out; a.gamma_out = d_gamma; a.applied_out = d_applied;
+  a.h = p.height / R; a.w = p.width / R;
+  const long long hw = (long long)a.h * a.w;
+  const bool v4 = p.width % 4 == 0 && aligned_to(d_depth_in, 16) && aligned_to(d_depth_out, 16);
+  const int tile_w = v4 ? 64 : 16;
+  const long long tiles_x = ((long long)p.width + tile_w - 1) / tile_w, tiles_y = ((long long)p.height + RV_DN_TILE_ROWS - 1) / RV_DN_TILE_ROWS;
+  const long long blocks = (long long)w->n * tiles_x * tiles_y;
+  const long long q = (hw + 3) / 4, total = (long long)w->n * q;
+  if (blocks > 0x7fffffffLL || (total + 255) / 256 > 0x7fffffffLL)
+    return fail(RV_ERR_VALUE, "rv_depth_noise: too many pixels for one launch");
+  a.Q = (int)q;
+  const size_t need = 2 * (size_t)w->n + (d_grid ? 0 : (size_t)w->n * (size_t)hw);
+  int rc = ensure_floats(w, &w->d_dn_scratch, &w->dn_scratch_cap, need); if (rc != RV_OK) return rc;
+  a.g = w->d_dn_scratch; a.flag = reinterpret_cast<uint32_t*>(w->d_dn_scratch + w->n);
+  a.grid = d_grid ? d_grid : w->d_dn_scratch + 2 * (size_t)w->n;
+  hipLaunchKernelGGL(k_depth_noise_draw, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, w->stream, w->d_cfg, a, total);
+  HIPCHK(hipGetLastError());
+  if (v4) hipLaunchKernelGGL(k_depth_noise_apply<4>, dim3((unsigned)blocks), dim3(256), 0, w->stream, a, (int)tiles_x, (int)tiles_y);
+  else hipLaunchKernelGGL(k_depth_noise_apply<1>, dim3((unsigned)blocks), dim3(256), 0, w->stream, a, (int)tiles_x, (int)tiles_y);
   HIPCHK(hipGetLastError());
   return RV_OK;
 }

@@ -36,6 +36,7 @@ SYMBOLS = [
     'rv_plan_reward', 'rv_plan_score',
     'rv_state_bytes', 'rv_state_save', 'rv_state_load', 'rv_branch', 'rv_plan_simulate',
     'rv_cem_sample', 'rv_cem_refit',
+    'rv_depth_noise',
 ]
 
 _EXC = {abi.RV_ERR_VALUE: ValueError, abi.RV_ERR_STATE: RuntimeError,
@@ -179,7 +180,7 @@ def load():
                  'rv_query_contacts', 'rv_get_manifold_counts', 'rv_get_episode_returns'):
         getattr(lib, name).argtypes = [vp, vp]
     abi.bind_state_api(lib)
-    for api in (abi.ANTIPODAL_API, abi.CEM_API):
+    for api in (abi.ANTIPODAL_API, abi.CEM_API, abi.DEPTH_NOISE_API):
         for name, (res, args) in api.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, list(args)
@@ -251,6 +252,28 @@ def cem_params(**overrides):
     for k, v in overrides.items():
         if k not in names:
             raise TypeError('cem_params: unknown field %r' % (k,))
+        setattr(p, k, type(getattr(p, k))(v))
+    return p
+
+
+def depth_noise_params(config=None, **overrides):
+    """The ``rv_depth_noise_params`` of an ``OBSERVATION.DEPTH_NOISE`` config: a mapping with the keys GAMMA_SHAPE, PROB,
+    RESCALE_FACTOR, SIGMA, SEED (any of them may be missing: the defaults are those of the reference's ``gamma_noise`` /
+    ``gaussian_noise``: 1000, 0.5, 4, 0.005, and seed 0).  ``height`` / ``width`` / ``draw_index`` start at 0 -- ``World.
+    depth_noise`` fills the size in from the tensor -- and keyword arguments override fields by their C names.  A
+    RESCALE_FACTOR that is not an integer becomes -1, which the library refuses."""
+    cfg = dict(config or {})
+    unknown = set(cfg) - {'GAMMA_SHAPE', 'PROB', 'RESCALE_FACTOR', 'SIGMA', 'SEED'}
+    if unknown:
+        raise TypeError('depth_noise_params: unknown keys %s' % (sorted(unknown),))
+    r = cfg.get('RESCALE_FACTOR', 4)
+    p = abi.rv_depth_noise_params(height=0, width=0, draw_index=0, seed=int(cfg.get('SEED', 0)) & 0xFFFFFFFF,
+                                  gamma_shape=float(cfg.get('GAMMA_SHAPE', 1000.0)), prob=float(cfg.get('PROB', 0.5)),
+                                  rescale_factor=int(r) if float(r) == int(r) else -1, sigma=float(cfg.get('SIGMA', 0.005)))
+    names = [n for n, _ in abi.rv_depth_noise_params._fields_]
+    for k, v in overrides.items():
+        if k not in names:
+            raise TypeError('depth_noise_params: unknown field %r' % (k,))
         setattr(p, k, type(getattr(p, k))(v))
     return p
 
@@ -588,6 +611,35 @@ class World(object):
         check(self.lib.rv_cem_refit(self.h, C.byref(params), self._ptr(a), self._ptr(r), s, h,
                                     self._ptr(m), self._ptr(sd), None if el is None else self._ptr(el)))
         return m.reshape(shape), sd.reshape(shape), el
+
+    # -- the depth sensor noise model (include/rovat.h: rv_depth_noise)
+    def depth_noise(self, depth, params, out=None, record=False):
+        """rv_depth_noise: the gamma multiplier and the upsampled Gaussian grid of ``params`` (``depth_noise_params(...)``;
+        its height and width are taken from the tensor) on ``depth``, float32 [N, H, W] on the device.  ``out``: None for a
+        new tensor, or a float32 [N, H, W] tensor to write (``depth`` itself: in place).  Returns the noisy depth, or with
+        ``record=True`` (noisy depth, g float32 [N], applied uint8 [N], grid float32 [N, H / R, W / R]) -- the grid of an
+        env the noise was not applied to, and every grid with sigma 0, reads zero."""
+        torch = self.torch
+        d = torch.as_tensor(depth, dtype=torch.float32, device=self.device)
+        if d.dim() != 3 or int(d.shape[0]) != self.n:
+            raise ValueError('depth_noise: depth must be [N, H, W] with N = %d, got %s' % (self.n, tuple(d.shape)))
+        d = d.contiguous()
+        if out is None:
+            out = self._new(tuple(d.shape), torch.float32)
+        elif not (torch.is_tensor(out) and out.dtype == torch.float32 and out.device == d.device
+                  and tuple(out.shape) == tuple(d.shape) and out.is_contiguous()):
+            raise ValueError('depth_noise: out must be a contiguous float32 tensor like depth, on its device')
+        p = abi.rv_depth_noise_params.from_buffer_copy(params)
+        p.height, p.width = int(d.shape[1]), int(d.shape[2])
+        g = ap = grid = None
+        if record:
+            r = int(p.rescale_factor) if 1 <= int(p.rescale_factor) <= abi.RV_DN_MAX_RESCALE else 1
+            g = self._new((self.n,), torch.float32)
+            ap = self._new((self.n,), torch.uint8)
+            grid = torch.zeros((self.n, p.height // r, p.width // r), dtype=torch.float32, device=self.device)
+        check(self.lib.rv_depth_noise(self.h, C.byref(p), self._ptr(d), self._ptr(out), None if g is None else self._ptr(g),
+                                      None if ap is None else self._ptr(ap), None if grid is None else self._ptr(grid)))
+        return (out, g, ap, grid) if record else out
 
     # -- env states as data (include/rovat.h: rv_state_* / rv_branch / rv_plan_simulate)
     def state_bytes(self):

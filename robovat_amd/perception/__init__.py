@@ -5,3 +5,4 @@ projection math on the host.  The product observation path is on the device
 (``csrc/rv_dev_obs.h``)."""
 from robovat_amd.perception.camera import Camera, intrinsic_to_projection_matrix  # noqa: F401
 from robovat_amd.perception import point_cloud_utils  # noqa: F401
+from robovat_amd.perception import depth_utils  # noqa: F401
