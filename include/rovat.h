@@ -571,6 +571,54 @@ int  rv_depth_noise(rv_world* w, const rv_depth_noise_params* h_params, const fl
                     float* d_depth_out /* may be d_depth_in */, float* d_gamma /* [N] or NULL */,
                     uint8_t* d_applied /* [N] or NULL */, float* d_grid /* [N][H/R][W/R] or NULL */);
 
+/* ---- s aimed pushes per env as proposals for look-ahead: the reference's HeuristicPushSampler.sample(position,
+ *      body_mask, num_episodes, num_steps, num_samples) (heuristic_push_sampler.py:52-123) and a planning form of it.
+ *      A push starts at least start_margin from every body and has its start or its end within motion_margin of its
+ *      target body; an attempt is five uniform draws, tested as rv_policy_heuristic tests it; the arithmetic is written
+ *      out operation for operation in csrc/rv_dev_push_sampler.h.  Read of an env: the positions, the body count and
+ *      the two counters of its last observation; nothing is changed.
+ *      RV_HP_EPISODE: the target is body num_episodes % n_bodies and the direction lies within 45 degrees of
+ *      42 * num_episodes, as in the reference; the s candidates share rv_policy_heuristic's one sequence of attempts
+ *      per env, candidate k starting behind the attempt candidate k - 1 stopped at, each with a budget of max_attempts:
+ *      the first attempt that passes is taken (RV_HP_FOUND), else the last of the budget as drawn (RV_HP_EXHAUSTED).
+ *      Candidate 0 is rv_policy_heuristic's push bit for bit.  plan_index, step and seed must be 0 and copies 1.
+ *      RV_HP_SPREAD: env m of the world is copy m % copies of the SOURCE env with global id (env_id_offset + m) / copies
+ *      (a world rv_branch filled with s copies per env has copies = s and s x the source's env_id_offset); candidate k
+ *      has the index kg = (m % copies) * s + k, aims at body kg % n_bodies in a direction drawn from all of them, and has
+ *      its own attempts and budget, Philox keyed by the world's seed, the source's global id, plan_index, step, the
+ *      params' seed, kg and the attempt -- not by N, s, copies or by what else is in the world.  So s candidates of a
+ *      world and one candidate of each of its s branches are the same bits while the observations are.
+ *      RV_ERR_VALUE, with nothing launched: a grasp world, s outside [1, RV_HP_MAX_SAMPLES], copies < 1 or copies * s >
+ *      RV_HP_MAX_SAMPLES, env_id_offset not a multiple of copies, max_attempts outside [1, RV_HP_MAX_ATTEMPTS], plan_index
+ *      outside [0, 2^24), step outside [0, 64), an unknown mode, RV_HP_EPISODE with plan_index, step or seed not 0 or
+ *      copies not 1, a negative or NaN margin, a missing required pointer, a buffer that is not 4-byte aligned. ---- */
+#define RV_HP_MAX_SAMPLES 1024
+#define RV_HP_MAX_ATTEMPTS 32768
+#define RV_HP_EPISODE 0
+#define RV_HP_SPREAD  1
+#define RV_HP_FOUND 1
+#define RV_HP_EXHAUSTED 0
+typedef struct rv_push_proposal_params {
+  int32_t  mode;                          /* RV_HP_EPISODE / RV_HP_SPREAD                               */
+  int32_t  plan_index, step;              /* Philox: the env.step() being planned, the step of the plan */
+  int32_t  copies;                        /* envs of this world per source env                          */
+  int32_t  max_attempts;                  /* per candidate                                              */
+  uint32_t seed;                          /* the policy's seed, on top of the world's                   */
+  float    start_margin, motion_margin;   /* the reference's defaults: 0.05, 0.01                       */
+} rv_push_proposal_params;
+/* d_actions [M][s][G][4] (M = the world's n_envs): a candidate's (start x, start y, motion x, motion y) in each of the G
+ * goal steps; d_status [M][s]: RV_HP_FOUND / RV_HP_EXHAUSTED.  Asynchronous on the world's stream. */
+int  rv_policy_heuristic_multi(rv_world* w, const rv_push_proposal_params* h_params, int32_t s,
+                               float* d_actions /* [M][s][G][4] */, int32_t* d_status /* [M][s] or NULL */);
+/* rv_plan_simulate with the actions drawn instead of given, each step from the branch's own simulated state:
+ * rv_branch(plan, src, s), then for t = 0 .. h - 1 { RV_HP_SPREAD proposals on the plan world, one per branch, with
+ * copies = h_params->copies * s and step = h_params->step + t, into slice t of d_actions; the actions of step t;
+ * rv_step_macro; record }.  Outputs, stream ordering and refusals as rv_plan_simulate, and those above for h_params (mode
+ * must be RV_HP_SPREAD, step + h <= 64); the plan world needs env_id_offset = s x the source's.  src is only read. */
+int  rv_plan_propose(rv_world* plan, rv_world* src, const rv_push_proposal_params* h_params, int32_t s, int32_t h,
+                     float* d_actions /* out [N][s][h][G][4] */, float* d_states, float* d_rewards,
+                     uint8_t* d_dones, int32_t* d_status /* [N][s][h] or NULL */);
+
 /* ---- Simulator.step x n (simulator.py:94-103): ControllableBody.update +
  *      BulletPhysics.step (bullet_physics.py:106-109), no phase machine. ---- */
 int  rv_step_sub(rv_world* w, int32_t n_substeps);

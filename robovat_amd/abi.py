@@ -253,6 +253,28 @@ DEPTH_NOISE_API = {
 }
 
 
+RV_HP_MAX_SAMPLES = 1024
+RV_HP_MAX_ATTEMPTS = 32768
+RV_HP_EPISODE, RV_HP_SPREAD = 0, 1
+RV_HP_FOUND, RV_HP_EXHAUSTED = 1, 0
+
+
+class rv_push_proposal_params(C.Structure):
+    _fields_ = [
+        ('mode', i32), ('plan_index', i32), ('step', i32), ('copies', i32), ('max_attempts', i32), ('seed', C.c_uint32),
+        ('start_margin', f32), ('motion_margin', f32),
+    ]
+
+
+# rv_policy_heuristic_multi: world, h_params, s, d_actions, d_status; rv_plan_propose: plan world, source world, h_params,
+# s, h, d_actions, d_states, d_rewards, d_dones, d_status (include/rovat.h); lib.load() binds them from here
+PUSH_PROPOSAL_API = {
+    'rv_policy_heuristic_multi': (C.c_int, [C.c_void_p, C.POINTER(rv_push_proposal_params), i32, C.c_void_p, C.c_void_p]),
+    'rv_plan_propose': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(rv_push_proposal_params), i32, i32,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
+
 # the env-state entry points of include/rovat.h (rv_state_* / rv_branch / rv_plan_simulate): name -> (restype, argtypes);
 # lib.load() binds them from here.  Worlds and device buffers are void pointers.
 STATE_API = {

@@ -31,6 +31,7 @@
 #include "rv_dev_plan.h"
 #include "rv_dev_cem.h"
 #include "rv_dev_depth_noise.h"
+#include "rv_dev_push_sampler.h"
 
 using namespace rv;
 
@@ -1343,6 +1344,81 @@ int rv_plan_simulate(rv_world* plan, rv_world* src, const float* d_actions, int3
   if ((long long)w->n * G * 4 > 0x7fffffffLL || (long long)w->n * RV_MAXB > 0x7fffffffLL) return fail(RV_ERR_VALUE, "rv_plan_simulate: too many envs for one launch");
   rc = branch_copy(plan, src, s); if (rc != RV_OK) return rc;
   for (int t = 0; t < h; ++t) {
+    hipLaunchKernelGGL(k_plan_actions, dim3((unsigned)((w->n * G * 4 + 255) / 256)), dim3(256), 0, w->stream, w->d_envs, w->n, d_actions, G, (int)h, t);
+    HIPCHK(hipGetLastError());
+    rc = launch_env<MODE_MACRO>(w, nullptr, 0, 0, 0, 0, 0, 0); if (rc != RV_OK) return rc;
+    if (d_states || d_rewards || d_dones) {
+      hipLaunchKernelGGL(k_plan_record, dim3((unsigned)((w->n * RV_MAXB + 255) / 256)), dim3(256), 0, w->stream, w->d_envs, w->n, (int)h, t, d_states, d_rewards, d_dones);
+      HIPCHK(hipGetLastError());
+    }
+  }
+  return RV_OK;
+}
+// the checks rv_policy_heuristic_multi and rv_plan_propose share: `w` is the world the kernel reads, p the params it is
+// launched with (rv_plan_propose: copies already x s, step the last one), s the candidates per env of w
+static int hp_check(const rv_world* w, const rv_push_proposal_params& p, int32_t s, const std::string& me) {
+  if (w->cfg.env_type == RV_ENV_GRASP) return fail(RV_ERR_VALUE, me + ": a PushEnv world only");
+  if (s < 1 || s > RV_HP_MAX_SAMPLES) return fail(RV_ERR_VALUE, me + ": s outside [1, RV_HP_MAX_SAMPLES]");
+  if (p.mode != RV_HP_EPISODE && p.mode != RV_HP_SPREAD) return fail(RV_ERR_VALUE, me + ": unknown mode");
+  if (p.copies < 1 || (long long)p.copies * s > RV_HP_MAX_SAMPLES) return fail(RV_ERR_VALUE, me + ": copies < 1 or copies * s > RV_HP_MAX_SAMPLES");
+  if (w->cfg.env_id_offset % p.copies != 0) return fail(RV_ERR_VALUE, me + ": env_id_offset is not a multiple of copies");
+  if (p.max_attempts < 1 || p.max_attempts > RV_HP_MAX_ATTEMPTS) return fail(RV_ERR_VALUE, me + ": max_attempts outside [1, RV_HP_MAX_ATTEMPTS]");
+  if (p.plan_index < 0 || p.plan_index >= RV_HP_MAX_PLAN_INDEX) return fail(RV_ERR_VALUE, me + ": plan_index outside [0, 2^24)");
+  if (p.step < 0 || p.step >= RV_HP_MAX_STEP) return fail(RV_ERR_VALUE, me + ": step outside [0, 64)");
+  if (p.mode == RV_HP_EPISODE && (p.plan_index != 0 || p.step != 0 || p.seed != 0u || p.copies != 1))
+    return fail(RV_ERR_VALUE, me + ": RV_HP_EPISODE takes plan_index, step and seed 0 and copies 1");
+  if (!(p.start_margin >= 0.0f) || !(p.motion_margin >= 0.0f)) return fail(RV_ERR_VALUE, me + ": a margin is negative or NaN");
+  if ((long long)w->n * s > 0x7fffffffLL) return fail(RV_ERR_VALUE, me + ": too many candidates for one launch");
+  return RV_OK;
+}
+// rows of (env, candidate) are (m * s + k) * h + t (csrc/rv_dev_push_sampler.h)
+static int hp_launch(rv_world* w, const rv_push_proposal_params& p, int s, int h, int t, float* d_actions, int32_t* d_status) {
+  HpArgs a;
+  a.p = p; a.actions = d_actions; a.status = d_status; a.S = s; a.h = h; a.t = t;
+  if (p.mode == RV_HP_EPISODE) {
+    hipLaunchKernelGGL(k_push_proposals_episode, dim3((unsigned)w->n), dim3(64), 0, w->stream, w->d_envs, w->n, w->d_cfg, a);
+  } else {
+    const long long waves = (long long)w->n * s;
+    hipLaunchKernelGGL(k_push_proposals_spread, dim3((unsigned)((waves + RV_HP_WAVES - 1) / RV_HP_WAVES)), dim3(64 * RV_HP_WAVES), 0, w->stream,
+                       w->d_envs, w->n, w->d_cfg, a);
+  }
+  HIPCHK(hipGetLastError());
+  return RV_OK;
+}
+int rv_policy_heuristic_multi(rv_world* w, const rv_push_proposal_params* h_params, int32_t s, float* d_actions, int32_t* d_status) {
+  WCHK(w);
+  if (!h_params) return fail(RV_ERR_VALUE, "rv_policy_heuristic_multi: null params");
+  int rc = hp_check(w, *h_params, s, "rv_policy_heuristic_multi"); if (rc != RV_OK) return rc;
+  NEED(d_actions, "rv_policy_heuristic_multi");
+  if (!aligned_to(d_actions, 4) || !aligned_to(d_status, 4)) return fail(RV_ERR_VALUE, "rv_policy_heuristic_multi: the buffers must be 4-byte aligned");
+  return hp_launch(w, *h_params, s, 1, 0, d_actions, d_status);
+}
+int rv_plan_propose(rv_world* plan, rv_world* src, const rv_push_proposal_params* h_params, int32_t s, int32_t h,
+                    float* d_actions, float* d_states, float* d_rewards, uint8_t* d_dones, int32_t* d_status) {
+  WCHK(src); WCHK(plan);
+  rv_world* w = plan;
+  if (src->cfg.env_type == RV_ENV_GRASP || plan->cfg.env_type == RV_ENV_GRASP) return fail(RV_ERR_VALUE, "rv_plan_propose: PushEnv worlds only");
+  int rc = branch_check(plan, src, s, "rv_plan_propose"); if (rc != RV_OK) return rc;
+  if (h < 1) return fail(RV_ERR_VALUE, "rv_plan_propose: h must be positive");
+  if (!h_params) return fail(RV_ERR_VALUE, "rv_plan_propose: null params");
+  if (h_params->mode != RV_HP_SPREAD) return fail(RV_ERR_VALUE, "rv_plan_propose: the mode must be RV_HP_SPREAD");
+  if (h_params->copies < 1 || (long long)h_params->copies * s > RV_HP_MAX_SAMPLES) return fail(RV_ERR_VALUE, "rv_plan_propose: copies < 1 or copies * s > RV_HP_MAX_SAMPLES");
+  if ((long long)plan->cfg.env_id_offset != (long long)src->cfg.env_id_offset * s) return fail(RV_ERR_VALUE, "rv_plan_propose: the plan world needs env_id_offset = s x the source's");
+  // the kernel reads the plan world: one candidate per branch env, copies x s envs per source env, the last step's key
+  rv_push_proposal_params p = *h_params;
+  p.copies = h_params->copies * s;
+  if (h_params->step < 0 || (long long)h_params->step + h > RV_HP_MAX_STEP) return fail(RV_ERR_VALUE, "rv_plan_propose: step < 0 or step + h > 64");
+  p.step = h_params->step + h - 1;
+  rc = hp_check(plan, p, 1, "rv_plan_propose"); if (rc != RV_OK) return rc;
+  NEED(d_actions, "rv_plan_propose");
+  if (!aligned_to(d_actions, 4) || !aligned_to(d_states, 8) || !aligned_to(d_rewards, 4) || !aligned_to(d_status, 4))
+    return fail(RV_ERR_VALUE, "rv_plan_propose: the states must be 8-byte aligned, actions, rewards and status 4-byte aligned");
+  const int G = w->cfg.num_goal_steps > 0 ? w->cfg.num_goal_steps : 1;
+  if ((long long)w->n * G * 4 > 0x7fffffffLL || (long long)w->n * RV_MAXB > 0x7fffffffLL) return fail(RV_ERR_VALUE, "rv_plan_propose: too many envs for one launch");
+  rc = branch_copy(plan, src, s); if (rc != RV_OK) return rc;
+  for (int t = 0; t < h; ++t) {
+    p.step = h_params->step + t;
+    rc = hp_launch(w, p, 1, (int)h, t, d_actions, d_status); if (rc != RV_OK) return rc;
     hipLaunchKernelGGL(k_plan_actions, dim3((unsigned)((w->n * G * 4 + 255) / 256)), dim3(256), 0, w->stream, w->d_envs, w->n, d_actions, G, (int)h, t);
     HIPCHK(hipGetLastError());
     rc = launch_env<MODE_MACRO>(w, nullptr, 0, 0, 0, 0, 0, 0); if (rc != RV_OK) return rc;

@@ -208,8 +208,42 @@ class VecPushEnv(object):
         p = lib.cem_params(plan_index=self._macro_index, n_elites=int(num_elites), alpha=float(alpha), min_std=float(min_std))
         return self.world.cem_refit(c, returns, mean, std, p)
 
+    def _proposal_params(self, mode, step, seed, max_attempts, start_margin, motion_margin):
+        """the key of an env's proposals: 'spread' draws are keyed by the index of the env.step() being planned, 'episode'
+        draws by the observation's counters alone (the library refuses a step or seed there)"""
+        from robovat_amd import lib
+        spread = mode in ('spread', abi.RV_HP_SPREAD)
+        return lib.push_proposal_params(mode, plan_index=self._macro_index if spread else 0, step=int(step),
+                                        seed=int(seed) & 0xFFFFFFFF, max_attempts=int(max_attempts),
+                                        start_margin=float(start_margin), motion_margin=float(motion_margin))
+
+    def sample_heuristic_candidates(self, num_samples, mode='spread', step=0, seed=0, max_attempts=20000,
+                                    start_margin=0.05, motion_margin=0.01):
+        """``num_samples`` aimed pushes per env from the last observation (``lib.World.policy_heuristic_multi``): each starts
+        ``start_margin`` clear of every body and touches its target body within ``motion_margin``.  ``mode`` 'spread':
+        candidate k aims at body k % n_bodies in any direction, keyed by the world's seed, the global env id, the index
+        of the env.step() being planned, ``step``, ``seed`` and k -- the same whatever else is in the batch.  'episode':
+        the reference's ``HeuristicPushSampler.sample(..., num_samples)``, candidate 0 being ``sample_heuristic_actions``'
+        push.  Returns (actions float32 [N, S] + action shape, found bool [N, S]: False where ``max_attempts`` ran out
+        and the last attempt is returned as drawn)."""
+        p = self._proposal_params(mode, step, seed, max_attempts, start_margin, motion_margin)
+        a, st = self.world.policy_heuristic_multi(p, int(num_samples))
+        return a.reshape((self.num_envs, int(a.shape[1])) + self.action_shape), st == abi.RV_HP_FOUND
+
+    def propose_plans(self, num_samples, horizon, seed=0, max_attempts=20000, start_margin=0.05, motion_margin=0.01):
+        """Look ahead with aimed pushes: ``num_samples`` plans of ``horizon`` steps per env, tried on copies of the env
+        (``lib.World.plan_propose``).  Step t of a plan is the 'spread' candidate of ``sample_heuristic_candidates`` drawn
+        from that copy's own state after step t - 1, so every push of a plan aims at where the bodies then are.  The
+        envs themselves do not change.  Returns (actions float32 [N, S, H] + action shape, states, rewards, dones as
+        ``simulate_plans``, found bool [N, S, H])."""
+        if int(num_samples) < 1:
+            raise ValueError('propose_plans: num_samples must be positive')
+        p = self._proposal_params('spread', 0, seed, max_attempts, start_margin, motion_margin)
+        a, st, r, d, status = self._plan_world(int(num_samples)).plan_propose(self.world, p, int(num_samples), int(horizon))
+        return a.reshape(tuple(a.shape[:3]) + self.action_shape), st, r, d.bool(), status == abi.RV_HP_FOUND
+
     def rollout(self, n_steps, auto_reset=True, record=True):
-        before = self.world.env_counters().cpu().numpy()[:, [2, 4]] if (auto_reset and self._physics is not None) else None
+        before =self.world.env_counters().cpu().numpy()[:, [2, 4]] if (auto_reset and self._physics is not None) else None
         out = self.world.rollout(n_steps, self._macro_index, auto_reset, record)
         if before is not None:
             # the host mirror of the user constraints is dropped only when an env really was reset
@@ -373,6 +407,17 @@ class PushEnv(object):
         r = r[None] if r.dim() == 1 else r
         m, s, e = self._vec.refit_plan_distribution(c, r, self._one(mean), self._one(std), num_elites, alpha, min_std)
         return m[0], s[0], e[0]
+
+    def sample_heuristic_candidates(self, num_samples, mode='spread', step=0, seed=0, max_attempts=20000,
+                                    start_margin=0.05, motion_margin=0.01):
+        """``VecPushEnv.sample_heuristic_candidates`` for this env.  Returns (actions [S] + action shape, found [S])."""
+        a, f = self._vec.sample_heuristic_candidates(num_samples, mode, step, seed, max_attempts, start_margin, motion_margin)
+        return a[0], f[0]
+
+    def propose_plans(self, num_samples, horizon, seed=0, max_attempts=20000, start_margin=0.05, motion_margin=0.01):
+        """``VecPushEnv.propose_plans`` for this env.  Returns (actions [S, H] + action shape, states [S, H, RV_MAXB, 2],
+        rewards [S, H], dones [S, H], found [S, H])."""
+        return tuple(x[0] for x in self._vec.propose_plans(num_samples, horizon, seed, max_attempts, start_margin, motion_margin))
 
     def _one(self, x):
         """[H] + action shape -> [1, H] + action shape"""

@@ -37,6 +37,7 @@ SYMBOLS = [
     'rv_state_bytes', 'rv_state_save', 'rv_state_load', 'rv_branch', 'rv_plan_simulate',
     'rv_cem_sample', 'rv_cem_refit',
     'rv_depth_noise',
+    'rv_policy_heuristic_multi', 'rv_plan_propose',
 ]
 
 _EXC = {abi.RV_ERR_VALUE: ValueError, abi.RV_ERR_STATE: RuntimeError,
@@ -180,7 +181,7 @@ def load():
                  'rv_query_contacts', 'rv_get_manifold_counts', 'rv_get_episode_returns'):
         getattr(lib, name).argtypes = [vp, vp]
     abi.bind_state_api(lib)
-    for api in (abi.ANTIPODAL_API, abi.CEM_API, abi.DEPTH_NOISE_API):
+    for api in (abi.ANTIPODAL_API, abi.CEM_API, abi.DEPTH_NOISE_API, abi.PUSH_PROPOSAL_API):
         for name, (res, args) in api.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, list(args)
@@ -252,6 +253,21 @@ def cem_params(**overrides):
     for k, v in overrides.items():
         if k not in names:
             raise TypeError('cem_params: unknown field %r' % (k,))
+        setattr(p, k, type(getattr(p, k))(v))
+    return p
+
+
+def push_proposal_params(mode='spread', **overrides):
+    """An ``rv_push_proposal_params``: ``mode`` 'spread' / 'episode' (or RV_HP_SPREAD / RV_HP_EPISODE), plan_index 0, step
+    0, copies 1, max_attempts 20000, seed 0 and the reference's margins (start 0.05, motion 0.01).  Keyword arguments
+    override fields."""
+    modes = {'episode': abi.RV_HP_EPISODE, 'spread': abi.RV_HP_SPREAD}
+    p = abi.rv_push_proposal_params(mode=modes.get(mode, mode), plan_index=0, step=0, copies=1, max_attempts=20000, seed=0,
+                                    start_margin=0.05, motion_margin=0.01)
+    names = [n for n, _ in abi.rv_push_proposal_params._fields_]
+    for k, v in overrides.items():
+        if k not in names:
+            raise TypeError('push_proposal_params: unknown field %r' % (k,))
         setattr(p, k, type(getattr(p, k))(v))
     return p
 
@@ -700,6 +716,34 @@ class World(object):
         d = self._new((n, s, h), self.torch.uint8)
         check(self.lib.rv_plan_simulate(self.h, src.h, self._ptr(a), s, h, self._ptr(st), self._ptr(r), self._ptr(d)))
         return st, r, d
+
+    # -- aimed pushes as proposals for look-ahead (include/rovat.h: rv_policy_heuristic_multi / rv_plan_propose)
+    def policy_heuristic_multi(self, params, s):
+        """rv_policy_heuristic_multi: ``s`` aimed pushes for every env of this world.  ``params``:
+        ``push_proposal_params(...)``.  Returns (actions float32 [M, s, G, 4], status int32 [M, s]: abi.RV_HP_FOUND /
+        abi.RV_HP_EXHAUSTED)."""
+        s = int(s)
+        rows = min(max(s, 1), abi.RV_HP_MAX_SAMPLES)      # (the library refuses an s outside [1, RV_HP_MAX_SAMPLES])
+        a = self._new((self.n, rows, self.G, 4), self.torch.float32)
+        st = self._new((self.n, rows), self.torch.int32)
+        check(self.lib.rv_policy_heuristic_multi(self.h, C.byref(params), s, self._ptr(a), self._ptr(st)))
+        return a, st
+
+    def plan_propose(self, src, params, s, h):
+        """rv_plan_propose with this world as the plan world: ``s`` plans of ``h`` aimed pushes per env of ``src``, each
+        push drawn from its branch's own simulated state; ``src`` is only read.  ``params``: ``push_proposal_params(...)``
+        in 'spread' mode.  Returns (actions float32 [N, s, h, G, 4], states float32 [N, s, h, RV_MAXB, 2], rewards float32
+        [N, s, h], dones uint8 [N, s, h] -- as ``plan_simulate`` -- and status int32 [N, s, h])."""
+        s, h = int(s), int(h)
+        n, rs, rh = src.n, max(s, 1), max(h, 1)      # (the library refuses s < 1 and h < 1)
+        a = self._new((n, rs, rh, self.G, 4), self.torch.float32)
+        st = self._new((n, rs, rh, abi.RV_MAXB, 2), self.torch.float32)
+        r = self._new((n, rs, rh), self.torch.float32)
+        d = self._new((n, rs, rh), self.torch.uint8)
+        status = self._new((n, rs, rh), self.torch.int32)
+        check(self.lib.rv_plan_propose(self.h, src.h, C.byref(params), s, h, self._ptr(a), self._ptr(st), self._ptr(r),
+                                       self._ptr(d), self._ptr(status)))
+        return a, st, r, d, status
 
     # -- state
     def _get(self, fn, shape, dtype):

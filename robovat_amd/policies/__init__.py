@@ -148,6 +148,51 @@ class ShootingPushPolicy(Policy):
         return self.plan(observation)[0]
 
 
+class HeuristicShootingPushPolicy(Policy):
+    """``ShootingPushPolicy`` with informed candidates: per env ``num_samples`` plans of ``horizon`` aimed pushes
+    (``VecPushEnv.propose_plans``: every push starts ``start_margin`` clear of the bodies and touches one of them within
+    ``motion_margin``, candidate k aiming at body k % n_bodies, each step drawn from the simulated state its plan has
+    reached; Philox keyed by the world's seed, the global env id, the env.step() being planned, the step of the plan,
+    ``seed`` and k -- an env plans the same whatever else is in the batch, and the same again until it steps) are tried
+    on copies of the env and ranked exactly as ``ShootingPushPolicy`` ranks them: ``score_plans`` with discount
+    ``gamma``, or the discounted rewards the env gave.  The action is the first one of the best plan, the lowest index
+    among equals; the env does not change.  Kept: ``last_best`` [N], ``last_returns`` [N, S] and ``last_found``
+    [N, S, H] (False where a push ran out of ``max_attempts``).  ``env``: a ``VecPushEnv`` or a ``PushEnv``."""
+
+    def __init__(self, env, num_samples, horizon, gamma=1.0, seed=0, max_attempts=20000, start_margin=0.05,
+                 motion_margin=0.01, use_plan_reward=True, is_high_level=False, config=None):
+        super(HeuristicShootingPushPolicy, self).__init__(env, config)
+        if int(num_samples) < 1 or int(horizon) < 1:
+            raise ValueError('HeuristicShootingPushPolicy: num_samples and horizon must be positive')
+        self._vec = getattr(env, '_vec', env)      # (a PushEnv is a VecPushEnv of one)
+        self._single = self._vec is not env
+        self.num_samples, self.horizon, self.gamma, self.seed = int(num_samples), int(horizon), float(gamma), int(seed)
+        self.max_attempts, self.start_margin, self.motion_margin = int(max_attempts), float(start_margin), float(motion_margin)
+        self.use_plan_reward, self.is_high_level = bool(use_plan_reward), bool(is_high_level)
+        self._torch = self._vec.world.torch
+        self.last_best = self.last_returns = self.last_found = None
+
+    def plan(self, observation=None):
+        """(actions [N] + action shape, best int32 [N]) -- for a PushEnv one action and an int."""
+        t, v = self._torch, self._vec
+        cand, states, rewards, _, found = v.propose_plans(self.num_samples, self.horizon, self.seed, self.max_attempts,
+                                                          self.start_margin, self.motion_margin)
+        if self.use_plan_reward:
+            returns, _, best = v.score_plans(states, None, self.is_high_level, self.gamma)
+        else:
+            disc = t.full((self.horizon,), self.gamma, device=v.device, dtype=t.float32) ** t.arange(self.horizon, device=v.device)
+            returns = (rewards * disc).sum(dim=2)
+            best = returns.argmax(dim=1).to(t.int32)      # (the first of equal maxima)
+        self.last_best, self.last_returns, self.last_found = best, returns, found
+        actions = cand[t.arange(v.num_envs, device=v.device), best.long(), 0]
+        if self._single:
+            return actions[0].cpu().numpy(), int(best[0])
+        return actions, best
+
+    def _action(self, observation):
+        return self.plan(observation)[0]
+
+
 class CEMPushPolicy(Policy):
     """Cross-entropy-method model-predictive control with the simulator as the model.  Per env a normal distribution over
     action sequences of ``horizon`` steps starts at mean 0, std ``init_std``; ``num_iterations`` times, ``num_samples``

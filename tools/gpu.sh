@@ -22,6 +22,8 @@
 #   cem            tools/cem_bench.py: the CEM planner's two kernels against torch, and the goal-rate comparison
 #   depth_noise    tools/depth_noise_bench.py: rv_depth_noise against a device copy and a torch restatement; then the two
 #                  kernels' own durations from a profiler run of the same tool
+#   push_proposals tools/push_proposals_bench.py: rv_policy_heuristic_multi against a torch restatement, and the goal rate of
+#                  HeuristicShootingPushPolicy next to the other planners
 #   lanes          SQ_THREAD_CYCLES_VALU / SQ_ACTIVE_INST_VALU lane-utilisation pass (headline and no-deactivation)
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}; TAG=$1; shift
 O=$R/gpurun_out/$TAG; mkdir -p $O; cd $R
@@ -64,6 +66,9 @@ for STAGE in "$@"; do
     cem)
       timeout -k 10 900 python tools/cem_bench.py --out $O/cem_bench.txt > $O/cem_bench.log 2>&1; echo "cem rc=$?" >> $O/time.txt
       tail -20 $O/cem_bench.txt ;;
+    push_proposals)
+      timeout -k 10 900 python tools/push_proposals_bench.py --out $O/push_proposals_bench.txt > $O/push_proposals_bench.log 2>&1; echo "push_proposals rc=$?" >> $O/time.txt
+      tail -20 $O/push_proposals_bench.txt ;;
     depth_noise)
       timeout -k 10 600 python tools/depth_noise_bench.py --out $O/depth_noise_bench.txt > $O/depth_noise_bench.log 2>&1 &&
         timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $O/depth_noise_prof -o dn --output-format csv -- python tools/depth_noise_bench.py --iters 10 --warmup 2 > $O/depth_noise_prof.log 2>&1
