@@ -2750,16 +2750,61 @@ RV_DEV void coast_measure_clearances(Shared& S, const Consts& K, const int col) 
   const float zc = cmin[2] - table_z - margin - cqd;
   const float sc = fsqrtr(sphere_box_dist2(cc, tc, th)) - (colr + brkc);
   const float tclear = zc > sc ? zc : sc;                 // either test rejecting is enough
+  // Body clearance: the largest travel bound D of the box's vertices under which no sleeper can be woken, stored
+  // doubled (the contract of clr_b, kept by the fused loop, coast_budget, coast_finish and the look-ahead's slack:
+  // "D is admissible while clr_b > 2 D").
+  //
+  // What a coasted substep skips.  Coasting needs every body asleep (any_on == 0 on entry), so the regular substep
+  // it replaces would be sim_substep_light with no body on, and that one
+  //   (1) never enters the arm-far test (it wants a body that is on), so none of its culls -- the sleeper's sphere
+  //       test of round 5 included -- is evaluated, on the boxes of this run or of any other; the first regular
+  //       substep after a run finds kin_fresh == 0 and computes frames and boxes again before anything reads them;
+  //   (2) computes the boxes and the arm-table gate (atflag): clr_t, untouched here;
+  //   (3) runs wake stage 1 per (sleeping movable body b, box): flagged iff aabb_aabb_dist2(baabb[b], box) < R^2,
+  //       R = wake_range + 2 margin, and sep[b][col] - travel is not positive.  No awake body means no neighbour
+  //       wakes a sleeper either, so with every pair unflagged the substep is quiet: returns 0, no heavy part.
+  // So it is (3) that has to say "no" for every substep of the run.  Let every vertex of the box have travelled at
+  // most D since these kinematics; then every face of its AABB (a max / min over the vertices) has moved at most D,
+  // and with g_k >= 0 the gaps between the two AABBs along the axes, g_k' >= g_k - D after the travel:
+  //   (a) D <= g_max - R:  the AABB distance is at least its largest axis gap, >= g_max - D >= R.  Not flagged.
+  //   (b) D <= (d - R) / sqrt 3 with d = |g|:  g = (g - D)+ + min(g, D) componentwise, and the second vector is no
+  //       longer than sqrt 3 D, so the distance after the travel, |(g' )+| >= |(g - D)+| >= d - sqrt 3 D >= R.  Not flagged.
+  //       ((a) and (b) are the two ends of one family; the former 0.5 (d - R) was (b) with 2 for sqrt 3.)
+  //   (c) D < sep:  sep is a lower bound of (hull distance - contact range) from a distance query, hull to box, not AABB
+  //       to AABB: 1-Lipschitz in the travel, which is how coast_finish and stage 1 itself take travel off it.
+  //       sep - D > 0: stage 1 clears the flag (`nr && sep > 0').
+  // Any one of the three suffices, so the admissible travel is their max.  Rounding: g_k, d - R and the products
+  // below are off by a few ulp of a coordinate (< 1e-6 m), the D of every test is the path-length bound times 1.02
+  // plus at least 1e-6, and 0.5773 < 1 / sqrt 3; the 0.9999 keeps `clr_b > 2 D' strict.
   float bclear = 1e30f;
+#ifdef RV_EMU_COUNT
+  int cnt_term = -1;
+#endif
 #pragma unroll
   for (int b = 0; b < RV_MAXB; ++b) {
     if (!use[b]) continue;
     // (wake_range: the smaller breaking threshold of the body and the box, capped by the wake gap)
     const float wr = fminr(fminr(breaking * (rad[b] - margin), brkc), wake_gap);
-    float d = fsqrtr(aabb_aabb_dist2(bb[b], bb[b] + 3, cmin, cmax)) - (wr + 2.0f * margin);
-    d = fmaxr(d, sep[b]);   // the distance bound left by the last wake query, if better
-    bclear = fminr(bclear, d);
+    const float R = wr + 2.0f * margin;
+    float gmax = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) gmax = fmaxr(gmax, fmaxr(cmin[k] - bb[b][3 + k], bb[b][k] - cmax[k]));
+    const float d = fsqrtr(aabb_aabb_dist2(bb[b], bb[b] + 3, cmin, cmax)) - R;
+    float adm = fmaxr(gmax - R, 0.5773f * d);
+    adm = fmaxr(adm, sep[b]);   // the distance bound left by the last wake query, if better
+#ifdef RV_EMU_COUNT
+    if (2.0f * adm * 0.9999f < bclear) {      // which of (a), (b), (c) speaks for the nearest body; 3: (b) with three positive gaps
+      int pos = 0;
+      for (int k = 0; k < 3; ++k) pos += fmaxr(cmin[k] - bb[b][3 + k], bb[b][k] - cmax[k]) > 0.0f;
+      cnt_term = adm == sep[b] ? 2 : (adm == gmax - R ? 0 : (pos == 3 ? 3 : 1));
+    }
+#endif
+    bclear = fminr(bclear, 2.0f * adm * 0.9999f);
   }
+#ifdef RV_EMU_COUNT
+  // (tools/emu_counts.py, tests/test_coast_bounds_emu.py: measurements in which the body clearance is the smaller one, by term)
+  if (cnt_term >= 0 && 0.5f * bclear < tclear) rv_emu_dbg[8 + cnt_term] += 1;
+#endif
   // Levers for the travel bound of the fused loop.  ccoef (the length of the chain from the joint
   // to the box, valid in any configuration) is what a folded arm never reaches: the distance R_j
   // from joint j's origin to the farthest point of the box, measured now, changes only through the
@@ -2907,6 +2952,42 @@ RV_DEV float col_travelled(const Shared& S, const Consts& K, const int col) {
 // after coasted substeps: FK / colliders are NOT refreshed: consecutive chunks run on the clearances left
 // over (arm_refresh_kinematics is called by whoever needs frames or fresh clearances)
 RV_DEV void coast_finish(Shared& S, const Consts& K) {
+#if RV_ON_DEVICE
+  // (device: one straight-line lane phase.  Every load up front, col_travelled's chain sum unrolled over the limb joints
+  // with a predicate -- the rolled loop's trip count depends on the lane, with two dependent LDS loads per trip --
+  // and the stores last.  The additions are in col_travelled's order, so the values are those of the host text below,
+  // which is what the emulator runs, bit for bit: THE RULE of DESIGN.md §10)
+  {
+    const int lane = (int)threadIdx.x;
+    DevEnv& e = S.e;
+    const bool is_sep = lane >= 8 && lane < 8 + RV_MAXB * RV_NCOL, is_clr = lane >= 48 && lane < 48 + RV_NCOL;
+    const int t = is_sep ? lane - 8 : 0, b = t / RV_NCOL;
+    const int col = is_sep ? t - b * RV_NCOL : (is_clr ? lane - 48 : 0);
+    const int f = K.arm->col_frame[col]; const int fl = f < 7 ? f : 7;
+    float jt[RV_NJ], jl[RV_NLIMB + 1];
+#pragma unroll
+    for (int j = 0; j < RV_NJ; ++j) jt[j] = S.s.jtravel[j];
+#pragma unroll
+    for (int j = 0; j <= RV_NLIMB; ++j) jl[j] = S.s.jlen[j];
+    const float sep = S.s.sep[b][col], clt = S.s.clr_t[col], clb = S.s.clr_b[col];
+    float tr = 0.0f, reach = S.s.colext[col];
+#pragma unroll
+    for (int j = RV_NLIMB; j >= 0; --j) {
+      if (j <= fl) {
+        if (j < RV_NLIMB) tr += reach * jt[j];
+        reach += jl[j];
+      }
+    }
+    if (f >= 8) tr += f == 8 ? jt[7] : jt[8];
+    const float d = tr * 1.02f + 1e-6f;
+    if (lane == 0) e.flag_arm_table = 0;
+    if (lane >= 1 && lane <= RV_MAXB) e.flag_arm_body[lane - 1] = 0;
+    if (is_sep) S.s.sep[b][col] = fmaxr(sep - d, 0.0f);
+    if (is_clr) { S.s.clr_t[col] = clt - d; S.s.clr_b[col] = clb - 2.0f * d; }
+    if (lane == 63) S.s.kin_fresh = 0;
+  }
+  RV_WAVE_SYNC();
+#else
   RV_LANES_BEGIN
     DevEnv& e = S.e;
     if (lane == 0) e.flag_arm_table = 0;
@@ -2923,6 +3004,7 @@ RV_DEV void coast_finish(Shared& S, const Consts& K) {
     }
     if (lane == 63) S.s.kin_fresh = 0;
   RV_LANES_END
+#endif
 }
 RV_DEV void coast_substeps(Shared& S, const Consts& K, const int m, const int kidx) {
 #ifdef RV_EMU_COUNT
@@ -3019,8 +3101,17 @@ RV_DEV CoastCtl coast_ctl_load(const Shared& S, const Consts& K) {
   CoastCtl C;
   C.lt_on = e.lt.active; C.jt_on = e.jt.active; C.applied = S.s.jt_applied; C.from_ik = e.jt.from_ik;
   C.lt_has_stop = e.lt.has_stop; C.lt_more = e.lt.has_pose || e.lt.nq != 0; C.jt_has_stop = e.jt.has_stop;
+#if RV_ON_DEVICE
+  // (device, whole wave: lane i looks at entry i of the joint target -- no loop with a loaded trip count between the
+  // scalar loads of this function, which are then issued together)
+  {
+    const int lane = (int)threadIdx.x;
+    C.jt_limb = __builtin_amdgcn_ballot_w64(lane < RV_NJ && lane < e.jt.n_idx && e.jt.idx[lane < RV_NJ ? lane : 0] < RV_NLIMB) != 0;
+  }
+#else
   C.jt_limb = 0;
   for (int i = 0; i < e.jt.n_idx; ++i) if (e.jt.idx[i] < RV_NLIMB) C.jt_limb = 1;
+#endif
   C.lt_stop = e.lt.stop_t; C.jt_stop = e.jt.stop_t; C.dt = K.cfg->dt;
   C.interrupt = S.s.interrupt; C.has_budget = S.s.has_budget; C.max_phase_steps = S.s.max_phase_steps;
   C.grasp = K.cfg->env_type == RV_ENV_GRASP; C.g_phase = e.phase; C.g_action_steps = e.num_action_steps;
@@ -3055,6 +3146,21 @@ RV_DEV int coast_fused(Shared& S, const Consts& K, const int steps_check, const 
   if (K.stop_after != 0 || !S.e.arm_enabled) return 0;
   const int fresh = S.s.kin_fresh;
   if (!fresh && !S.s.clr_valid) return 0;
+#if RV_ON_DEVICE
+  // (device: lane b asks for body b, lane col for box col -- one load per lane, a ballot and a 16-lane min, as the
+  // solver entry's mask phase does it, for 12 + 20 words read by the whole wave.  min is exact: the order is free)
+  {
+    const int lane = (int)threadIdx.x;
+    if (__builtin_amdgcn_ballot_w64(body_on(S.e, lane & (RV_MAXB - 1)) != 0) != 0) return 0;
+    if (!fresh) {       // clearances left over by the last chunk: anything left at all?
+      const int col = lane < RV_NCOL ? lane : 0;
+      float cm = fminr(S.s.clr_t[col], 0.5f * S.s.clr_b[col]);
+      cm = row_ror_min<8>(cm); cm = row_ror_min<4>(cm); cm = row_ror_min<2>(cm); cm = row_ror_min<1>(cm);
+      const float cmin = rdlane(cm, 0);
+      if (!(cmin > 2e-4f)) { *tick_pending = 1; return 0; }
+    }
+  }
+#else
   {
     int any_on = 0;
 #pragma unroll
@@ -3066,6 +3172,7 @@ RV_DEV int coast_fused(Shared& S, const Consts& K, const int steps_check, const 
     for (int col = 0; col < RV_NCOL; ++col) cmin = fminr(cmin, fminr(S.s.clr_t[col], 0.5f * S.s.clr_b[col]));
     if (!(cmin > 2e-4f)) { RV_CNT(11, 1) *tick_pending = 1; return 0; }
   }
+#endif
   RV_LANES_BEGIN
     if (fresh && lane < RV_NCOL) coast_measure_clearances(S, K, lane);
     if (lane == 63) { S.s.clr_valid = 1; S.s.fused_n = 0; }
@@ -3106,8 +3213,14 @@ RV_DEV int coast_fused(Shared& S, const Consts& K, const int steps_check, const 
   // this lane's joint in the joint target
   int tgt = 0; float tpos = 0.0f;
   {
+    // (every entry loaded up front and the search unrolled with a predicate: a rolled loop had a loaded trip count and
+    // two dependent LDS loads per trip.  Entries past n_idx hold whatever was there: never looked at)
     const int n_idx = uni(e.jt.n_idx);
-    for (int i = 0; i < n_idx; ++i) if (e.jt.idx[i] == lane) { tgt = 1; tpos = e.jt.pos[i]; }
+    int ix[RV_NJ]; float ps[RV_NJ];
+#pragma unroll
+    for (int i = 0; i < RV_NJ; ++i) { ix[i] = e.jt.idx[i]; ps[i] = e.jt.pos[i]; }
+#pragma unroll
+    for (int i = 0; i < RV_NJ; ++i) if (i < n_idx && ix[i] == lane) { tgt = 1; tpos = ps[i]; }
   }
   const float pos_thr = unif(e.jt.pos_thr), vel_thr = unif(e.jt.vel_thr);
   const int has_vel = uni(e.jt.has_vel);
