@@ -619,6 +619,55 @@ int  rv_plan_propose(rv_world* plan, rv_world* src, const rv_push_proposal_param
                      float* d_actions /* out [N][s][h][G][4] */, float* d_states, float* d_rewards,
                      uint8_t* d_dones, int32_t* d_status /* [N][s][h] or NULL */);
 
+/* ---- s route-following pushes per env as proposals for look-ahead (no counterpart in the reference): pushes that move
+ *      body 0 -- the target of the crossing and insertion tasks -- one cell along the layout towards the goal.  The tiles
+ *      span a grid of 8 x 8 cells, cell r * 8 + c centred at tile_offset + (r, c) * tile_size; walkable are the region
+ *      and goal tiles (RV_TASK_CROSSING) or every cell but the region tiles, goal tiles included (RV_TASK_INSERTION).
+ *      The route field D[64] (rv_get_route_field; a function of the rv_config alone, computed at a world's first use and
+ *      kept) is the number of 4-neighbour hops through walkable cells to the nearest goal cell: 0 on a goal cell, 255 on
+ *      a cell that is not walkable or reaches no goal.  A push aims from body 0 at the centre of the neighbour, one hop
+ *      closer to the goal, of the walkable cell nearest to body 0 (at that cell's own centre on a goal cell, at the nearest
+ *      goal centre where no goal is reached), rotated by a jitter angle; it starts `back` behind the body on that line,
+ *      `lat` to its side, and is (distance to the aim + back) * f long.  An attempt draws the jitter from +- angle_jitter,
+ *      back from [back_lo, back_hi], lat from +- lateral and f from [length_lo, length_hi] -- four uniforms of one Philox
+ *      block keyed as RV_HP_SPREAD keys its attempts, on a stream id of its own -- and passes if its start is farther than
+ *      start_margin from every movable body; the first that passes is taken (RV_HP_FOUND), else the last of max_attempts
+ *      as drawn (RV_HP_EXHAUSTED).  With keep_nominal the candidate with index kg = 0 draws nothing: no jitter, back =
+ *      (back_lo + back_hi) / 2, lat = 0, f = 1.  copies, kg and the source env's global id are those of RV_HP_SPREAD, so
+ *      s candidates of a world and one candidate of each of its s branches are the same bits while the observations are.
+ *      An env whose body 0 is not movable gets a zero action and RV_HP_EXHAUSTED.  Read of an env: the positions and the
+ *      body count of its last observation; nothing is changed.  The arithmetic is written out operation for operation in
+ *      csrc/rv_dev_push_route.h.  The first of these calls on a world launches the field's kernel and waits for it, once
+ *      (not inside a stream capture); after that they are asynchronous on the world's stream.
+ *      RV_ERR_VALUE, with nothing launched: a grasp world, a task other than crossing or insertion, n_goal == 0 (or a
+ *      tile count outside [0, RV_MAXTILES]), a region or goal tile that is no integer pair of the 8 x 8 grid, s outside
+ *      [1, RV_HP_MAX_SAMPLES], copies < 1 or copies * s > RV_HP_MAX_SAMPLES, env_id_offset not a multiple of copies,
+ *      max_attempts outside [1, RV_HP_MAX_ATTEMPTS], plan_index outside [0, 2^24), step outside [0, 64), a negative or NaN
+ *      start_margin, angle_jitter or lateral, back_lo > back_hi, length_lo > length_hi, length_lo < 0 (a NaN among them
+ *      too), a missing required pointer, a buffer that is not 4-byte aligned. ---- */
+typedef struct rv_push_route_params {
+  int32_t  plan_index, step;              /* Philox: the env.step() being planned, the step of the plan */
+  int32_t  copies;                        /* envs of this world per source env                          */
+  int32_t  max_attempts;                  /* per candidate                                              */
+  uint32_t seed;                          /* the policy's seed, on top of the world's                   */
+  int32_t  keep_nominal;                  /* candidate kg = 0 is the push without jitter                */
+  float    start_margin;                  /* the start's clearance from every body                      */
+  float    angle_jitter;                  /* radians, to either side of the aim direction               */
+  float    back_lo, back_hi;              /* how far behind body 0 the push starts                      */
+  float    lateral;                       /* the start's offset to either side of the aim line          */
+  float    length_lo, length_hi;          /* the push length as a fraction of (distance + back)         */
+} rv_push_route_params;
+int  rv_get_route_field(rv_world* w, uint8_t* d_out /* [64] */);
+/* d_actions [M][s][G][4], d_status [M][s] as rv_policy_heuristic_multi.  Asynchronous on the world's stream. */
+int  rv_policy_route_multi(rv_world* w, const rv_push_route_params* h_params, int32_t s,
+                           float* d_actions /* [M][s][G][4] */, int32_t* d_status /* [M][s] or NULL */);
+/* rv_plan_propose with route-following pushes: the same loop, step t drawn with copies = h_params->copies * s and step =
+ * h_params->step + t from the branch's own simulated state.  Outputs, stream ordering and refusals as rv_plan_propose,
+ * and those above for h_params (step + h <= 64). */
+int  rv_plan_propose_route(rv_world* plan, rv_world* src, const rv_push_route_params* h_params, int32_t s, int32_t h,
+                           float* d_actions /* out [N][s][h][G][4] */, float* d_states, float* d_rewards,
+                           uint8_t* d_dones, int32_t* d_status /* [N][s][h] or NULL */);
+
 /* ---- Simulator.step x n (simulator.py:94-103): ControllableBody.update +
  *      BulletPhysics.step (bullet_physics.py:106-109), no phase machine. ---- */
 int  rv_step_sub(rv_world* w, int32_t n_substeps);

@@ -275,7 +275,30 @@ PUSH_PROPOSAL_API = {
 }
 
 
-# the env-state entry points of include/rovat.h (rv_state_* / rv_branch / rv_plan_simulate): name -> (restype, argtypes);
+RV_PR_GRID = 8
+RV_PR_NONE = 255
+
+
+class rv_push_route_params(C.Structure):
+    _fields_ = [
+        ('plan_index', i32), ('step', i32), ('copies', i32), ('max_attempts', i32), ('seed', C.c_uint32), ('keep_nominal', i32),
+        ('start_margin', f32), ('angle_jitter', f32), ('back_lo', f32), ('back_hi', f32), ('lateral', f32),
+        ('length_lo', f32), ('length_hi', f32),
+    ]
+
+
+# rv_get_route_field: world, d_out; rv_policy_route_multi: world, h_params, s, d_actions, d_status; rv_plan_propose_route:
+# plan world, source world, h_params, s, h, d_actions, d_states, d_rewards, d_dones, d_status (include/rovat.h); lib.load()
+# binds them from here
+PUSH_ROUTE_API = {
+    'rv_get_route_field': (C.c_int, [C.c_void_p, C.c_void_p]),
+    'rv_policy_route_multi': (C.c_int, [C.c_void_p, C.POINTER(rv_push_route_params), i32, C.c_void_p, C.c_void_p]),
+    'rv_plan_propose_route': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(rv_push_route_params), i32, i32,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
+
+# the env-state entry points of include/rovat.h (rv_state_*/ rv_branch / rv_plan_simulate): name -> (restype, argtypes);
 # lib.load() binds them from here.  Worlds and device buffers are void pointers.
 STATE_API = {
     'rv_state_bytes': (i64, [C.c_void_p]),

@@ -132,7 +132,9 @@ RV_DEV HpScene hp_scene(const DevEnv& e, const rv_config* c, const rv_push_propo
   sc.start_margin = p.start_margin; sc.motion_margin = p.motion_margin;
   return sc;
 }
-RV_DEV void hp_write(const HpArgs& A, int G, size_t row, const float (&a)[4], int status) {
+// (Args: HpArgs, or the PrArgs of rv_dev_push_route.h -- the same row layout)
+template <class Args>
+RV_DEV void hp_write(const Args& A, int G, size_t row, const float (&a)[4], int status) {
   for (int g2 = 0; g2 < G; ++g2) {
     float* o = A.actions + (row * (size_t)G + (size_t)g2) * 4;
     o[0] = a[0]; o[1] = a[1]; o[2] = a[2]; o[3] = a[3];

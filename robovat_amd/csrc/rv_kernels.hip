@@ -32,6 +32,7 @@
 #include "rv_dev_cem.h"
 #include "rv_dev_depth_noise.h"
 #include "rv_dev_push_sampler.h"
+#include "rv_dev_push_route.h"
 
 using namespace rv;
 
@@ -587,6 +588,9 @@ struct rv_world {
   // rv_depth_noise: [N] multipliers, [N] flags (as words), then the noise grid when the caller gives none (floats; grown
   // on demand)
   float* d_dn_scratch; size_t dn_scratch_cap;
+  // rv_get_route_field / rv_policy_route_multi: D[64] and walkable[64] of the config's tiles (rv_dev_push_route.h), made at
+  // first use -- no setter changes the tile fields of cfg after rv_create
+  uint8_t* d_route;
 };
 
 static thread_local std::string g_err;
@@ -805,6 +809,7 @@ int rv_create(const rv_config* cfg, const rv_scene* scene, int device, rv_world*
   w->d_snaps = nullptr; w->n_snaps_cap = 0;
   w->d_ap_depth = nullptr; w->ap_depth_cap = 0; w->d_ap_scratch = nullptr; w->ap_scratch_cap = 0;
   w->d_dn_scratch = nullptr; w->dn_scratch_cap = 0;
+  w->d_route = nullptr;
   w->scene_hash = bytes_hash(scene, sizeof(rv_scene));
   {
     // one wave per env: with more envs than SIMDs the two-waves-per-SIMD build of the env kernel pays
@@ -851,6 +856,7 @@ int rv_destroy(rv_world* w) {
   if (w->d_ap_depth) (void)hipFree(w->d_ap_depth);
   if (w->d_ap_scratch) (void)hipFree(w->d_ap_scratch);
   if (w->d_dn_scratch) (void)hipFree(w->d_dn_scratch);
+  if (w->d_route) (void)hipFree(w->d_route);
   (void)hipEventDestroy(w->ev0); (void)hipEventDestroy(w->ev1); (void)hipEventDestroy(w->ev_state);
   delete w;
   return RV_OK;
@@ -1393,32 +1399,38 @@ int rv_policy_heuristic_multi(rv_world* w, const rv_push_proposal_params* h_para
   if (!aligned_to(d_actions, 4) || !aligned_to(d_status, 4)) return fail(RV_ERR_VALUE, "rv_policy_heuristic_multi: the buffers must be 4-byte aligned");
   return hp_launch(w, *h_params, s, 1, 0, d_actions, d_status);
 }
-int rv_plan_propose(rv_world* plan, rv_world* src, const rv_push_proposal_params* h_params, int32_t s, int32_t h,
-                    float* d_actions, float* d_states, float* d_rewards, uint8_t* d_dones, int32_t* d_status) {
+// rv_plan_propose and rv_plan_propose_route, the part that does not know the proposal kernel.  Params: the params struct of
+// either (both have copies and step); `mode_ok`: what the caller asks of *h_params beyond the ranges; `check(plan, p, 1,
+// me)`: the range checks on the params the kernel is launched with (copies already x s, step the last one); `propose(plan,
+// p, h, t)`: the launch that writes slice t of d_actions / d_status from the plan world's state, p.step = the step of t
+extern "C++" template <class Params, class ModeOk, class Check, class Propose>
+static int plan_propose_run(rv_world* plan, rv_world* src, const Params* h_params, int32_t s, int32_t h, float* d_actions, float* d_states,
+                            float* d_rewards, uint8_t* d_dones, int32_t* d_status, const char* who, ModeOk mode_ok, Check check, Propose propose) {
   WCHK(src); WCHK(plan);
+  const std::string me(who);
   rv_world* w = plan;
-  if (src->cfg.env_type == RV_ENV_GRASP || plan->cfg.env_type == RV_ENV_GRASP) return fail(RV_ERR_VALUE, "rv_plan_propose: PushEnv worlds only");
-  int rc = branch_check(plan, src, s, "rv_plan_propose"); if (rc != RV_OK) return rc;
-  if (h < 1) return fail(RV_ERR_VALUE, "rv_plan_propose: h must be positive");
-  if (!h_params) return fail(RV_ERR_VALUE, "rv_plan_propose: null params");
-  if (h_params->mode != RV_HP_SPREAD) return fail(RV_ERR_VALUE, "rv_plan_propose: the mode must be RV_HP_SPREAD");
-  if (h_params->copies < 1 || (long long)h_params->copies * s > RV_HP_MAX_SAMPLES) return fail(RV_ERR_VALUE, "rv_plan_propose: copies < 1 or copies * s > RV_HP_MAX_SAMPLES");
-  if ((long long)plan->cfg.env_id_offset != (long long)src->cfg.env_id_offset * s) return fail(RV_ERR_VALUE, "rv_plan_propose: the plan world needs env_id_offset = s x the source's");
+  if (src->cfg.env_type == RV_ENV_GRASP || plan->cfg.env_type == RV_ENV_GRASP) return fail(RV_ERR_VALUE, me + ": PushEnv worlds only");
+  int rc = branch_check(plan, src, s, who); if (rc != RV_OK) return rc;
+  if (h < 1) return fail(RV_ERR_VALUE, me + ": h must be positive");
+  if (!h_params) return fail(RV_ERR_VALUE, me + ": null params");
+  rc = mode_ok(*h_params); if (rc != RV_OK) return rc;
+  if (h_params->copies < 1 || (long long)h_params->copies * s > RV_HP_MAX_SAMPLES) return fail(RV_ERR_VALUE, me + ": copies < 1 or copies * s > RV_HP_MAX_SAMPLES");
+  if ((long long)plan->cfg.env_id_offset != (long long)src->cfg.env_id_offset * s) return fail(RV_ERR_VALUE, me + ": the plan world needs env_id_offset = s x the source's");
   // the kernel reads the plan world: one candidate per branch env, copies x s envs per source env, the last step's key
-  rv_push_proposal_params p = *h_params;
+  Params p = *h_params;
   p.copies = h_params->copies * s;
-  if (h_params->step < 0 || (long long)h_params->step + h > RV_HP_MAX_STEP) return fail(RV_ERR_VALUE, "rv_plan_propose: step < 0 or step + h > 64");
+  if (h_params->step < 0 || (long long)h_params->step + h > RV_HP_MAX_STEP) return fail(RV_ERR_VALUE, me + ": step < 0 or step + h > 64");
   p.step = h_params->step + h - 1;
-  rc = hp_check(plan, p, 1, "rv_plan_propose"); if (rc != RV_OK) return rc;
-  NEED(d_actions, "rv_plan_propose");
+  rc = check(plan, p, 1, me); if (rc != RV_OK) return rc;
+  if (!d_actions) return fail(RV_ERR_VALUE, me + ": null buffer");
   if (!aligned_to(d_actions, 4) || !aligned_to(d_states, 8) || !aligned_to(d_rewards, 4) || !aligned_to(d_status, 4))
-    return fail(RV_ERR_VALUE, "rv_plan_propose: the states must be 8-byte aligned, actions, rewards and status 4-byte aligned");
+    return fail(RV_ERR_VALUE, me + ": the states must be 8-byte aligned, actions, rewards and status 4-byte aligned");
   const int G = w->cfg.num_goal_steps > 0 ? w->cfg.num_goal_steps : 1;
-  if ((long long)w->n * G * 4 > 0x7fffffffLL || (long long)w->n * RV_MAXB > 0x7fffffffLL) return fail(RV_ERR_VALUE, "rv_plan_propose: too many envs for one launch");
+  if ((long long)w->n * G * 4 > 0x7fffffffLL || (long long)w->n * RV_MAXB > 0x7fffffffLL) return fail(RV_ERR_VALUE, me + ": too many envs for one launch");
   rc = branch_copy(plan, src, s); if (rc != RV_OK) return rc;
   for (int t = 0; t < h; ++t) {
     p.step = h_params->step + t;
-    rc = hp_launch(w, p, 1, (int)h, t, d_actions, d_status); if (rc != RV_OK) return rc;
+    rc = propose(w, p, (int)h, t); if (rc != RV_OK) return rc;
     hipLaunchKernelGGL(k_plan_actions, dim3((unsigned)((w->n * G * 4 + 255) / 256)), dim3(256), 0, w->stream, w->d_envs, w->n, d_actions, G, (int)h, t);
     HIPCHK(hipGetLastError());
     rc = launch_env<MODE_MACRO>(w, nullptr, 0, 0, 0, 0, 0, 0); if (rc != RV_OK) return rc;
@@ -1428,6 +1440,93 @@ int rv_plan_propose(rv_world* plan, rv_world* src, const rv_push_proposal_params
     }
   }
   return RV_OK;
+}
+int rv_plan_propose(rv_world* plan, rv_world* src, const rv_push_proposal_params* h_params, int32_t s, int32_t h,
+                    float* d_actions, float* d_states, float* d_rewards, uint8_t* d_dones, int32_t* d_status) {
+  return plan_propose_run(plan, src, h_params, s, h, d_actions, d_states, d_rewards, d_dones, d_status, "rv_plan_propose",
+    [](const rv_push_proposal_params& p) { return p.mode == RV_HP_SPREAD ? RV_OK : fail(RV_ERR_VALUE, "rv_plan_propose: the mode must be RV_HP_SPREAD"); },
+    hp_check,
+    [=](rv_world* w, const rv_push_proposal_params& p, int h_, int t) { return hp_launch(w, p, 1, h_, t, d_actions, d_status); });
+}
+
+// ---- route-following push proposals (csrc/rv_dev_push_route.h)
+// the config's tiles: what k_route_field and k_push_proposals_route rely on
+static int route_cfg_check(const rv_world* w, const std::string& me) {
+  const rv_config& c = w->cfg;
+  if (c.env_type == RV_ENV_GRASP) return fail(RV_ERR_VALUE, me + ": a PushEnv world only");
+  if (c.task != RV_TASK_CROSSING && c.task != RV_TASK_INSERTION) return fail(RV_ERR_VALUE, me + ": the task must be crossing or insertion");
+  if (c.n_goal < 1 || c.n_goal > RV_MAXTILES || c.n_region < 0 || c.n_region > RV_MAXTILES) return fail(RV_ERR_VALUE, me + ": n_goal outside [1, RV_MAXTILES] or n_region outside [0, RV_MAXTILES]");
+  for (int list = 0; list < 2; ++list) {
+    const float (*tiles)[2] = list ? c.goal : c.region;
+    const int n = list ? c.n_goal : c.n_region;
+    for (int j = 0; j < n; ++j)
+      for (int k = 0; k < 2; ++k) {
+        const float v = tiles[j][k];
+        if (!(v >= 0.0f && v <= (float)(RV_PR_GRID - 1)) || v != (float)(int)v) return fail(RV_ERR_VALUE, me + ": a region or goal tile is no integer pair of the 8 x 8 grid");
+      }
+  }
+  return RV_OK;
+}
+// the field of a world whose config passed route_cfg_check: made once, on the stream the world has at that moment, and
+// waited for -- the world may be given another stream later
+static int route_field(rv_world* w) {
+  if (w->d_route) return RV_OK;
+  uint8_t* d = nullptr;
+  HIPCHK(hipMalloc(&d, RV_PR_FIELD_BYTES));
+  hipLaunchKernelGGL(k_route_field, dim3(1), dim3(64), 0, w->stream, w->d_cfg, d);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipStreamSynchronize(w->stream);
+  if (e != hipSuccess) { (void)hipFree(d); return fail(RV_ERR_HIP, std::string("k_route_field: ") + hipGetErrorString(e)); }
+  w->d_route = d;
+  return RV_OK;
+}
+// the checks rv_policy_route_multi and rv_plan_propose_route share, as hp_check
+static int pr_check(const rv_world* w, const rv_push_route_params& p, int32_t s, const std::string& me) {
+  int rc = route_cfg_check(w, me); if (rc != RV_OK) return rc;
+  if (s < 1 || s > RV_HP_MAX_SAMPLES) return fail(RV_ERR_VALUE, me + ": s outside [1, RV_HP_MAX_SAMPLES]");
+  if (p.copies < 1 || (long long)p.copies * s > RV_HP_MAX_SAMPLES) return fail(RV_ERR_VALUE, me + ": copies < 1 or copies * s > RV_HP_MAX_SAMPLES");
+  if (w->cfg.env_id_offset % p.copies != 0) return fail(RV_ERR_VALUE, me + ": env_id_offset is not a multiple of copies");
+  if (p.max_attempts < 1 || p.max_attempts > RV_HP_MAX_ATTEMPTS) return fail(RV_ERR_VALUE, me + ": max_attempts outside [1, RV_HP_MAX_ATTEMPTS]");
+  if (p.plan_index < 0 || p.plan_index >= RV_HP_MAX_PLAN_INDEX) return fail(RV_ERR_VALUE, me + ": plan_index outside [0, 2^24)");
+  if (p.step < 0 || p.step >= RV_HP_MAX_STEP) return fail(RV_ERR_VALUE, me + ": step outside [0, 64)");
+  if (!(p.start_margin >= 0.0f) || !(p.angle_jitter >= 0.0f) || !(p.lateral >= 0.0f)) return fail(RV_ERR_VALUE, me + ": start_margin, angle_jitter or lateral is negative or NaN");
+  if (!(p.back_lo <= p.back_hi)) return fail(RV_ERR_VALUE, me + ": back_lo > back_hi (or a NaN)");
+  if (!(p.length_lo <= p.length_hi) || !(p.length_lo >= 0.0f)) return fail(RV_ERR_VALUE, me + ": length_lo > length_hi or length_lo < 0 (or a NaN)");
+  if ((long long)w->n * s > 0x7fffffffLL) return fail(RV_ERR_VALUE, me + ": too many candidates for one launch");
+  return RV_OK;
+}
+static int pr_launch(rv_world* w, const rv_push_route_params& p, int s, int h, int t, float* d_actions, int32_t* d_status) {
+  int rc = route_field(w); if (rc != RV_OK) return rc;
+  PrArgs a;
+  a.p = p; a.field = w->d_route; a.actions = d_actions; a.status = d_status; a.S = s; a.h = h; a.t = t;
+  const long long waves = (long long)w->n * s;
+  hipLaunchKernelGGL(k_push_proposals_route, dim3((unsigned)((waves + RV_HP_WAVES - 1) / RV_HP_WAVES)), dim3(64 * RV_HP_WAVES), 0, w->stream,
+                     w->d_envs, w->n, w->d_cfg, a);
+  HIPCHK(hipGetLastError());
+  return RV_OK;
+}
+int rv_get_route_field(rv_world* w, uint8_t* d_out) {
+  WCHK(w);
+  int rc = route_cfg_check(w, "rv_get_route_field"); if (rc != RV_OK) return rc;
+  NEED(d_out, "rv_get_route_field");
+  rc = route_field(w); if (rc != RV_OK) return rc;
+  HIPCHK(hipMemcpyAsync(d_out, w->d_route, RV_PR_CELLS, hipMemcpyDeviceToDevice, w->stream));
+  return RV_OK;
+}
+int rv_policy_route_multi(rv_world* w, const rv_push_route_params* h_params, int32_t s, float* d_actions, int32_t* d_status) {
+  WCHK(w);
+  if (!h_params) return fail(RV_ERR_VALUE, "rv_policy_route_multi: null params");
+  int rc = pr_check(w, *h_params, s, "rv_policy_route_multi"); if (rc != RV_OK) return rc;
+  NEED(d_actions, "rv_policy_route_multi");
+  if (!aligned_to(d_actions, 4) || !aligned_to(d_status, 4)) return fail(RV_ERR_VALUE, "rv_policy_route_multi: the buffers must be 4-byte aligned");
+  return pr_launch(w, *h_params, s, 1, 0, d_actions, d_status);
+}
+int rv_plan_propose_route(rv_world* plan, rv_world* src, const rv_push_route_params* h_params, int32_t s, int32_t h,
+                          float* d_actions, float* d_states, float* d_rewards, uint8_t* d_dones, int32_t* d_status) {
+  return plan_propose_run(plan, src, h_params, s, h, d_actions, d_states, d_rewards, d_dones, d_status, "rv_plan_propose_route",
+    [](const rv_push_route_params&) { return RV_OK; },
+    pr_check,
+    [=](rv_world* w, const rv_push_route_params& p, int h_, int t) { return pr_launch(w, p, 1, h_, t, d_actions, d_status); });
 }
 int rv_reward(rv_world* w, float* d_reward, uint8_t* d_done) { WCHK(w); SIMPLE_LAUNCH(k_reward, w->d_envs, w->n, d_reward, d_done); return RV_OK; }
 int rv_get_episode_returns(rv_world* w, float* d) { WCHK(w); NEED(d, "rv_get_episode_returns"); SIMPLE_LAUNCH(k_returns, w->d_envs, w->n, d); return RV_OK; }

@@ -242,6 +242,36 @@ class VecPushEnv(object):
         a, st, r, d, status = self._plan_world(int(num_samples)).plan_propose(self.world, p, int(num_samples), int(horizon))
         return a.reshape(tuple(a.shape[:3]) + self.action_shape), st, r, d.bool(), status == abi.RV_HP_FOUND
 
+    def _route_params(self, step, seed, route):
+        """``route``: fields of ``lib.push_route_params`` (max_attempts, keep_nominal, start_margin, angle_jitter, back_lo,
+        back_hi, lateral, length_lo, length_hi); the key is that of the 'spread' proposals"""
+        from robovat_amd import lib
+        for k in ('plan_index', 'step', 'seed', 'copies'):
+            if k in route:
+                raise TypeError('route proposals: %r is set by the env' % (k,))
+        return lib.push_route_params(plan_index=self._macro_index, step=int(step), seed=int(seed) & 0xFFFFFFFF, **route)
+
+    def sample_route_candidates(self, num_samples, step=0, seed=0, **route):
+        """``num_samples`` pushes per env that move body 0 -- the target of the crossing and insertion tasks -- one cell
+        along the layout towards the goal, from the last observation (``lib.World.policy_route_multi``).  Candidate 0 is
+        the push without jitter (``keep_nominal``); the others draw a direction, a back-off, a side offset and a length
+        around it, keyed as the 'spread' candidates of ``sample_heuristic_candidates``.  ``route``: the fields of
+        ``lib.push_route_params``.  Returns (actions float32 [N, S] + action shape, found bool [N, S]: False where no
+        attempt started ``start_margin`` clear of every body)."""
+        p = self._route_params(step, seed, route)
+        a, st = self.world.policy_route_multi(p, int(num_samples))
+        return a.reshape((self.num_envs, int(a.shape[1])) + self.action_shape), st == abi.RV_HP_FOUND
+
+    def propose_route_plans(self, num_samples, horizon, seed=0, **route):
+        """``propose_plans`` with the pushes of ``sample_route_candidates`` (``lib.World.plan_propose_route``): step t of a
+        plan aims from where body 0 is in that copy after step t - 1.  The envs themselves do not change.  Returns
+        (actions float32 [N, S, H] + action shape, states, rewards, dones as ``simulate_plans``, found bool [N, S, H])."""
+        if int(num_samples) < 1:
+            raise ValueError('propose_route_plans: num_samples must be positive')
+        p = self._route_params(0, seed, route)
+        a, st, r, d, status = self._plan_world(int(num_samples)).plan_propose_route(self.world, p, int(num_samples), int(horizon))
+        return a.reshape(tuple(a.shape[:3]) + self.action_shape), st, r, d.bool(), status == abi.RV_HP_FOUND
+
     def rollout(self, n_steps, auto_reset=True, record=True):
         before =self.world.env_counters().cpu().numpy()[:, [2, 4]] if (auto_reset and self._physics is not None) else None
         out = self.world.rollout(n_steps, self._macro_index, auto_reset, record)
@@ -418,6 +448,16 @@ class PushEnv(object):
         """``VecPushEnv.propose_plans`` for this env.  Returns (actions [S, H] + action shape, states [S, H, RV_MAXB, 2],
         rewards [S, H], dones [S, H], found [S, H])."""
         return tuple(x[0] for x in self._vec.propose_plans(num_samples, horizon, seed, max_attempts, start_margin, motion_margin))
+
+    def sample_route_candidates(self, num_samples, step=0, seed=0, **route):
+        """``VecPushEnv.sample_route_candidates`` for this env.  Returns (actions [S] + action shape, found [S])."""
+        a, f = self._vec.sample_route_candidates(num_samples, step, seed, **route)
+        return a[0], f[0]
+
+    def propose_route_plans(self, num_samples, horizon, seed=0, **route):
+        """``VecPushEnv.propose_route_plans`` for this env.  Returns (actions [S, H] + action shape, states [S, H, RV_MAXB,
+        2], rewards [S, H], dones [S, H], found [S, H])."""
+        return tuple(x[0] for x in self._vec.propose_route_plans(num_samples, horizon, seed, **route))
 
     def _one(self, x):
         """[H] + action shape -> [1, H] + action shape"""

@@ -38,6 +38,7 @@ SYMBOLS = [
     'rv_cem_sample', 'rv_cem_refit',
     'rv_depth_noise',
     'rv_policy_heuristic_multi', 'rv_plan_propose',
+    'rv_get_route_field', 'rv_policy_route_multi', 'rv_plan_propose_route',
 ]
 
 _EXC = {abi.RV_ERR_VALUE: ValueError, abi.RV_ERR_STATE: RuntimeError,
@@ -181,7 +182,7 @@ def load():
                  'rv_query_contacts', 'rv_get_manifold_counts', 'rv_get_episode_returns'):
         getattr(lib, name).argtypes = [vp, vp]
     abi.bind_state_api(lib)
-    for api in (abi.ANTIPODAL_API, abi.CEM_API, abi.DEPTH_NOISE_API, abi.PUSH_PROPOSAL_API):
+    for api in (abi.ANTIPODAL_API, abi.CEM_API, abi.DEPTH_NOISE_API, abi.PUSH_PROPOSAL_API, abi.PUSH_ROUTE_API):
         for name, (res, args) in api.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, list(args)
@@ -268,6 +269,20 @@ def push_proposal_params(mode='spread', **overrides):
     for k, v in overrides.items():
         if k not in names:
             raise TypeError('push_proposal_params: unknown field %r' % (k,))
+        setattr(p, k, type(getattr(p, k))(v))
+    return p
+
+
+def push_route_params(**overrides):
+    """An ``rv_push_route_params``: plan_index 0, step 0, copies 1, max_attempts 256, seed 0, keep_nominal 1, start_margin
+    0.05, angle_jitter 0.3, back_lo 0.08, back_hi 0.16, lateral 0.02, length_lo 0.8, length_hi 1.2 (the spreads are
+    unmeasured defaults around the one push that was tried).  Keyword arguments override fields."""
+    p = abi.rv_push_route_params(plan_index=0, step=0, copies=1, max_attempts=256, seed=0, keep_nominal=1, start_margin=0.05,
+                                 angle_jitter=0.3, back_lo=0.08, back_hi=0.16, lateral=0.02, length_lo=0.8, length_hi=1.2)
+    names = [n for n, _ in abi.rv_push_route_params._fields_]
+    for k, v in overrides.items():
+        if k not in names:
+            raise TypeError('push_route_params: unknown field %r' % (k,))
         setattr(p, k, type(getattr(p, k))(v))
     return p
 
@@ -743,6 +758,40 @@ class World(object):
         status = self._new((n, rs, rh), self.torch.int32)
         check(self.lib.rv_plan_propose(self.h, src.h, C.byref(params), s, h, self._ptr(a), self._ptr(st), self._ptr(r),
                                        self._ptr(d), self._ptr(status)))
+        return a, st, r, d, status
+
+    # -- route-following pushes as proposals (include/rovat.h: rv_get_route_field / rv_policy_route_multi / rv_plan_propose_route)
+    def route_field(self):
+        """rv_get_route_field: uint8 [8, 8], the hops from every cell of the layout's grid through walkable cells to the
+        nearest goal cell; abi.RV_PR_NONE where a cell is not walkable or reaches no goal."""
+        d = self._new((abi.RV_PR_GRID, abi.RV_PR_GRID), self.torch.uint8)
+        check(self.lib.rv_get_route_field(self.h, self._ptr(d)))
+        return d
+
+    def policy_route_multi(self, params, s):
+        """rv_policy_route_multi: ``s`` pushes of body 0 along the layout for every env of this world.  ``params``:
+        ``push_route_params(...)``.  Returns (actions float32 [M, s, G, 4], status int32 [M, s]: abi.RV_HP_FOUND /
+        abi.RV_HP_EXHAUSTED)."""
+        s = int(s)
+        rows = min(max(s, 1), abi.RV_HP_MAX_SAMPLES)      # (the library refuses an s outside [1, RV_HP_MAX_SAMPLES])
+        a = self._new((self.n, rows, self.G, 4), self.torch.float32)
+        st = self._new((self.n, rows), self.torch.int32)
+        check(self.lib.rv_policy_route_multi(self.h, C.byref(params), s, self._ptr(a), self._ptr(st)))
+        return a, st
+
+    def plan_propose_route(self, src, params, s, h):
+        """rv_plan_propose_route with this world as the plan world: ``plan_propose`` with the pushes of
+        ``policy_route_multi``.  ``params``: ``push_route_params(...)``.  Returns (actions, states, rewards, dones, status)
+        as ``plan_propose``."""
+        s, h = int(s), int(h)
+        n, rs, rh = src.n, max(s, 1), max(h, 1)      # (the library refuses s < 1 and h < 1)
+        a = self._new((n, rs, rh, self.G, 4), self.torch.float32)
+        st = self._new((n, rs, rh, abi.RV_MAXB, 2), self.torch.float32)
+        r = self._new((n, rs, rh), self.torch.float32)
+        d = self._new((n, rs, rh), self.torch.uint8)
+        status = self._new((n, rs, rh), self.torch.int32)
+        check(self.lib.rv_plan_propose_route(self.h, src.h, C.byref(params), s, h, self._ptr(a), self._ptr(st), self._ptr(r),
+                                             self._ptr(d), self._ptr(status)))
         return a, st, r, d, status
 
     # -- state

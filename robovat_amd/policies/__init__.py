@@ -193,6 +193,51 @@ class HeuristicShootingPushPolicy(Policy):
         return self.plan(observation)[0]
 
 
+class RouteShootingPushPolicy(Policy):
+    """``HeuristicShootingPushPolicy`` with candidates that know the layout: per env ``num_samples`` plans of ``horizon``
+    pushes that move body 0, the task's target, one cell along the tiles towards the goal
+    (``VecPushEnv.propose_route_plans``: candidate 0 is the push without jitter, the others vary its direction, back-off,
+    side offset and length; each step is drawn from the simulated state its plan has reached; keyed as the heuristic
+    proposals are) are tried on copies of the env and ranked exactly as ``ShootingPushPolicy`` ranks them: ``score_plans``
+    with discount ``gamma``, or the discounted rewards the env gave.  The action is the first one of the best plan, the
+    lowest index among equals; the env does not change.  ``route``: fields of ``lib.push_route_params`` (max_attempts,
+    keep_nominal, start_margin, angle_jitter, back_lo, back_hi, lateral, length_lo, length_hi).  Kept: ``last_best``
+    [N], ``last_returns`` [N, S] and ``last_found`` [N, S, H].  Crossing and insertion tasks only.  ``env``: a
+    ``VecPushEnv`` or a ``PushEnv``."""
+
+    def __init__(self, env, num_samples, horizon, gamma=1.0, seed=0, use_plan_reward=True, is_high_level=False, config=None,
+                 **route):
+        super(RouteShootingPushPolicy, self).__init__(env, config)
+        if int(num_samples) < 1 or int(horizon) < 1:
+            raise ValueError('RouteShootingPushPolicy: num_samples and horizon must be positive')
+        self._vec = getattr(env, '_vec', env)      # (a PushEnv is a VecPushEnv of one)
+        self._single = self._vec is not env
+        self.num_samples, self.horizon, self.gamma, self.seed = int(num_samples), int(horizon), float(gamma), int(seed)
+        self.route = dict(route)
+        self.use_plan_reward, self.is_high_level = bool(use_plan_reward), bool(is_high_level)
+        self._torch = self._vec.world.torch
+        self.last_best = self.last_returns = self.last_found = None
+
+    def plan(self, observation=None):
+        """(actions [N] + action shape, best int32 [N]) -- for a PushEnv one action and an int."""
+        t, v = self._torch, self._vec
+        cand, states, rewards, _, found = v.propose_route_plans(self.num_samples, self.horizon, self.seed, **self.route)
+        if self.use_plan_reward:
+            returns, _, best = v.score_plans(states, None, self.is_high_level, self.gamma)
+        else:
+            disc = t.full((self.horizon,), self.gamma, device=v.device, dtype=t.float32) ** t.arange(self.horizon, device=v.device)
+            returns = (rewards * disc).sum(dim=2)
+            best = returns.argmax(dim=1).to(t.int32)      # (the first of equal maxima)
+        self.last_best, self.last_returns, self.last_found = best, returns, found
+        actions = cand[t.arange(v.num_envs, device=v.device), best.long(), 0]
+        if self._single:
+            return actions[0].cpu().numpy(), int(best[0])
+        return actions, best
+
+    def _action(self, observation):
+        return self.plan(observation)[0]
+
+
 class CEMPushPolicy(Policy):
     """Cross-entropy-method model-predictive control with the simulator as the model.  Per env a normal distribution over
     action sequences of ``horizon`` steps starts at mean 0, std ``init_std``; ``num_iterations`` times, ``num_samples``

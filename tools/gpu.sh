@@ -24,6 +24,8 @@
 #                  kernels' own durations from a profiler run of the same tool
 #   push_proposals tools/push_proposals_bench.py: rv_policy_heuristic_multi against a torch restatement, and the goal rate of
 #                  HeuristicShootingPushPolicy next to the other planners
+#   push_route     tools/push_route_bench.py: rv_policy_route_multi against a torch restatement, and the goal rate of
+#                  RouteShootingPushPolicy next to the other planners on crossing layouts 0 to 2; the kernels' resources
 #   lanes          SQ_THREAD_CYCLES_VALU / SQ_ACTIVE_INST_VALU lane-utilisation pass (headline and no-deactivation)
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}; TAG=$1; shift
 O=$R/gpurun_out/$TAG; mkdir -p $O; cd $R
@@ -69,6 +71,14 @@ for STAGE in "$@"; do
     push_proposals)
       timeout -k 10 900 python tools/push_proposals_bench.py --out $O/push_proposals_bench.txt > $O/push_proposals_bench.log 2>&1; echo "push_proposals rc=$?" >> $O/time.txt
       tail -20 $O/push_proposals_bench.txt ;;
+    push_route)
+      timeout -k 10 900 python tools/push_route_bench.py --out $O/push_route_bench.txt > $O/push_route_bench.log 2>&1 &&
+        timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/push_route_prof -o pr --output-format csv -- python tools/push_route_bench.py --skip-rate --iters 10 --warmup 2 > $O/push_route_prof.log 2>&1
+      echo "push_route rc=$?" >> $O/time.txt
+      grep -h "Name\|route" $(find $O/push_route_prof -name '*kernel_stats.csv') > $O/push_route_kernel_stats.txt
+      python tools/kernel_resources.py > $O/kernel_resources_all.txt 2>&1
+      grep -h "^kernel\|route" $O/kernel_resources_all.txt > $O/push_route_kernel_resources.txt
+      tail -40 $O/push_route_bench.txt ;;
     depth_noise)
       timeout -k 10 600 python tools/depth_noise_bench.py --out $O/depth_noise_bench.txt > $O/depth_noise_bench.log 2>&1 &&
         timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $O/depth_noise_prof -o dn --output-format csv -- python tools/depth_noise_bench.py --iters 10 --warmup 2 > $O/depth_noise_prof.log 2>&1

@@ -1,0 +1,197 @@
+"""Route-following push proposals: what the proposal kernel costs, and what the proposals buy.
+
+    python tools/push_route_bench.py [--iters 30] [--warmup 5] [--out profiles/push_route_bench.txt]
+                                     [--skip-kernels] [--skip-rate] [--layouts 0 1 2]
+
+(a) rv_policy_route_multi at N = 1024 envs, S = 64 candidates, the defaults of lib.push_route_params, against what a user
+    would write in torch on the same device: the nearest walkable cell and the aim by argmin / gather over the 64 cells
+    (the field itself is handed to it), then a FIXED number of attempts (--attempts, 64: one round of the kernel) drawn
+    for all candidates at once, the margin test on all of them, the first success taken by an argmax over the flags.
+    The torch code is the yardstick, not the code under test, and it draws other numbers (torch's generator is a
+    stream, not a key).  The kernel is timed with the same budget and with the default one (256).  Timed alternately
+    with device events, warm-up first, the median of --iters calls each, min and max alongside; every figure includes the
+    binding's allocations.  No bar is set.
+(b) DESIGN.md 18's goal-rate experiment on crossing layouts 0 to 2: 64 envs, seed 5, one episode each of at most 8
+    steps, gamma 0.9.  RouteShootingPushPolicy at the simulated candidate steps per decision of section 16's rows (128: S
+    = 64, H = 2; 512: S = 128, H = 4) next to HeuristicShootingPushPolicy, ShootingPushPolicy, CEMPushPolicy and
+    RandomPolicy.  Not a timing, and no bar is set on it.
+"""
+import argparse
+import os
+import sys
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import numpy as np
+import torch
+
+from robovat_amd import abi, configs, lib, scenes
+from push_proposals_bench import alternate, make_policy, BUDGETS, GAMMA
+
+
+def walkable(cfg):
+    """bool [64]: the cells body 0 may be on (csrc/rv_dev_push_route.h)"""
+    crossing = cfg.task == abi.RV_TASK_CROSSING
+    w = np.zeros(64, bool) if crossing else np.ones(64, bool)
+    for j in range(cfg.n_region):
+        w[int(cfg.region[j][0]) * 8 + int(cfg.region[j][1])] = crossing
+    for j in range(cfg.n_goal):
+        w[int(cfg.goal[j][0]) * 8 + int(cfg.goal[j][1])] = True
+    return w
+
+
+def torch_route(pos, mask, field, walk, cx, cy, s, attempts, cfg, p, gen):
+    """pos [N, B, 2], mask [N, B] (1 = a body), field int64 [64], walk bool [64], cx / cy [64] -> (actions [N, s, 4],
+    found [N, s]): `attempts` tries per candidate at once"""
+    n, dev = pos.shape[0], pos.device
+    inf = torch.full((), float('inf'), device=dev)
+    p0 = pos[:, 0]
+    q = (cx[None] - p0[:, 0, None]) ** 2 + (cy[None] - p0[:, 1, None]) ** 2                  # [N, 64]
+    cur = torch.where(walk[None], q, inf).argmin(dim=1)
+    d_cur = field[cur]
+    r, c = cur // 8, cur % 8
+    nbr = torch.stack([cur + 8, cur - 8, cur + 1, cur - 1], dim=1)
+    valid = torch.stack([r < 7, r > 0, c < 7, c > 0], dim=1)
+    closer = valid & (field[nbr.clamp(0, 63)] == (d_cur - 1)[:, None])
+    step = nbr.gather(1, closer.to(torch.uint8).argmax(dim=1, keepdim=True))[:, 0].clamp(0, 63)
+    goal = torch.where((field == 0)[None], q, inf).argmin(dim=1)
+    aim = torch.where(d_cur == 0, cur, torch.where(d_cur == 255, goal, step))
+    v = torch.stack([cx[aim], cy[aim]], dim=1) - p0
+    dist = v.norm(dim=1)
+    far = dist > 1e-6
+    ux = torch.where(far, v[:, 0] / dist, torch.ones_like(dist))[:, None, None]
+    uy = torch.where(far, v[:, 1] / dist, torch.zeros_like(dist))[:, None, None]
+    u = torch.rand((4, n, s, attempts), generator=gen, device=dev, dtype=torch.float32)
+    jit = (u[0] * 2.0 - 1.0) * p.angle_jitter
+    back = p.back_lo + (p.back_hi - p.back_lo) * u[1]
+    lat = (u[2] * 2.0 - 1.0) * p.lateral
+    f = p.length_lo + (p.length_hi - p.length_lo) * u[3]
+    sn, co = torch.sin(jit), torch.cos(jit)
+    dx, dy = ux * co - uy * sn, ux * sn + uy * co
+    lo0, hi0, lo1, hi1 = cfg.cspace_low[0], cfg.cspace_high[0], cfg.cspace_low[1], cfg.cspace_high[1]
+    x = (p0[:, 0, None, None] - dx * back - dy * lat).clamp(lo0, hi0)
+    y = (p0[:, 1, None, None] - dy * back + dx * lat).clamp(lo1, hi1)
+    ln = (dist[:, None, None] + back) * f
+    m0 = (dx * (ln / cfg.translation_x)).clamp(-1.0, 1.0)
+    m1 = (dy * (ln / cfg.translation_y)).clamp(-1.0, 1.0)
+    s0 = ((x - 0.5 * (hi0 + lo0)) / (0.5 * (hi0 - lo0))).clamp(-1.0, 1.0)
+    s1 = ((y - 0.5 * (hi1 + lo1)) / (0.5 * (hi1 - lo1))).clamp(-1.0, 1.0)
+    good = torch.ones_like(x, dtype=torch.bool)
+    for b in range(pos.shape[1]):
+        d = torch.hypot(pos[:, b, 0, None, None] - x, pos[:, b, 1, None, None] - y)
+        good &= (d > p.start_margin) | (mask[:, b, None, None] == 0)
+    found = good.any(dim=2)
+    first = torch.where(found, good.to(torch.uint8).argmax(dim=2), torch.full_like(found, attempts - 1, dtype=torch.long))
+    actions = torch.stack([t.gather(2, first[..., None])[..., 0] for t in (s0, s1, m0, m1)], dim=-1)
+    return actions, found
+
+
+def kernels(say, n, s, attempts, iters, warmup):
+    scene, names = scenes.make_scene()
+    cfg = configs.make_rv_config(env_cfg=configs.push_env_config(TASK_NAME='crossing', LAYOUT_ID=0), n_envs=n, seed=5, shape_names=names)
+    w = lib.World(cfg, scene, device=0)
+    try:
+        w.reset()
+        obs = w.observe()
+        pos, mask = obs['position'][..., :2].contiguous(), obs['body_mask']
+        field = w.route_field().reshape(64).long()
+        walk = torch.as_tensor(walkable(cfg), device=w.device)
+        idx = torch.arange(64, device=w.device)
+        cx = cfg.tile_offset[0] + (idx // 8).float() * cfg.tile_size
+        cy = cfg.tile_offset[1] + (idx % 8).float() * cfg.tile_size
+        gen = torch.Generator(device=w.device); gen.manual_seed(1)
+        same = lib.push_route_params(plan_index=1, seed=1, max_attempts=attempts, keep_nominal=0)
+        full = lib.push_route_params(plan_index=1, seed=1, keep_nominal=0)
+        a_same, st_same = w.policy_route_multi(same, s)
+        _, st_full = w.policy_route_multi(full, s)
+        a_t, t_found = torch_route(pos, mask, field, walk, cx, cy, s, attempts, cfg, same, gen)
+        torch.cuda.synchronize()
+        # the two draw other numbers around the same nominal push: their candidates' means agree to the spread's size
+        gap = float((a_same[:, :, 0].mean(dim=1) - a_t.mean(dim=1)).abs().max())
+        t = alternate({'k_same': lambda: w.policy_route_multi(same, s), 'k_full': lambda: w.policy_route_multi(full, s),
+                       'torch': lambda: torch_route(pos, mask, field, walk, cx, cy, s, attempts, cfg, same, gen)}, iters, warmup)
+        say('--- N = %d envs, S = %d candidates, crossing layout 0, the defaults of push_route_params, no nominal candidate; %d calls each after %d warm-up'
+            % (n, s, iters, warmup))
+        row = '  %-58s median %9.4f ms   min %9.4f   max %9.4f'
+        say(row % (('rv_policy_route_multi, max_attempts %d (incl. the binding)' % attempts,) + t['k_same']))
+        say(row % (('rv_policy_route_multi, max_attempts %d (incl. the binding)' % full.max_attempts,) + t['k_full']))
+        say(row % (('torch: %d attempts per candidate at once, argmax' % attempts,) + t['torch']))
+        say('  torch / kernel at the same budget: %.1fx;  candidates found: kernel %.2f %% (budget %d), %.2f %% (budget %d), torch %.2f %%;'
+            ' largest gap between the per-env mean candidates of the two: %.4f'
+            % (t['torch'][0] / t['k_same'][0], 100.0 * float((st_same == 1).float().mean()), attempts,
+               100.0 * float((st_full == 1).float().mean()), full.max_attempts, 100.0 * float(t_found.float().mean()), gap))
+    finally:
+        w.close()
+
+
+def policy_of(name, env, budget):
+    from robovat_amd import policies
+    it, s, h = budget
+    if name == 'route':
+        return policies.RouteShootingPushPolicy(env, it * s, h, gamma=GAMMA, seed=1)
+    return make_policy(name, env, budget)
+
+
+def goal_rate(say, layout, budget, names, n=64, max_steps=8):
+    from robovat_amd.envs.push.push_env import VecPushEnv
+    it, s, h = budget
+    cfg = configs.push_env_config(TASK_NAME='crossing', LAYOUT_ID=layout, MAX_STEPS=max_steps)
+    say('--- crossing layout %d, %d envs, seed 5, one episode each of at most %d steps, gamma %.1f; %d simulated candidate steps per'
+        ' decision: Route-, Heuristic- and ShootingPushPolicy S = %d, H = %d; CEMPushPolicy I = %d, S = %d, H = %d'
+        ' (defaults otherwise)' % (layout, n, max_steps, GAMMA, it * s * h, it * s, h, it, s, h))
+    for name in names:
+        env = VecPushEnv(n, config=cfg, seed=5)
+        try:
+            env.reset()
+            policy = policy_of(name, env, budget)
+            wins = done_eps = steps = ineffective = useful = nominal = decisions = 0
+            for _ in range(max_steps):
+                env.step(policy.action(None))
+                st = env.stats()
+                wins += st['successes']; done_eps += st['episodes_done']
+                steps += st['env_steps']; ineffective += st['ineffective']; useful += st['useful']
+                if name == 'route':
+                    nominal += int((policy.last_best == 0).sum()); decisions += int(policy.last_best.numel())
+            extra = '' if name != 'route' else '; decisions that took the nominal candidate: %.1f %%' % (100.0 * nominal / max(decisions, 1))
+            say('  %-9s policy: %d of %d episodes reached the goal (%.1f %%), %d episodes ended, mean episode return %.2f;'
+                ' %d env steps, effective %.1f %%, useful %.1f %%%s'
+                % (name, wins, n, 100.0 * wins / n, done_eps, float(env.world.episode_returns().mean()), steps,
+                   100.0 * (steps - ineffective) / max(steps, 1), 100.0 * useful / max(steps, 1), extra))
+        finally:
+            env.close()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--iters', type=int, default=30)
+    ap.add_argument('--warmup', type=int, default=5)
+    ap.add_argument('--attempts', type=int, default=64)
+    ap.add_argument('--layouts', type=int, nargs='*', default=[0, 1, 2])
+    ap.add_argument('--policies', nargs='*', default=['route', 'heuristic', 'shooting', 'cem', 'random'])
+    ap.add_argument('--out', default=None)
+    ap.add_argument('--skip-kernels', action='store_true')
+    ap.add_argument('--skip-rate', action='store_true')
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit('push_route_bench: no GPU (a timing needs the device)')
+    lines = []
+
+    def say(text):
+        print(text, flush=True)
+        lines.append(text)
+        if args.out:
+            with open(args.out, 'w') as f:
+                f.write('\n'.join(lines) + '\n')
+    say('tools/push_route_bench.py --iters %d --warmup %d --attempts %d on %s'
+        % (args.iters, args.warmup, args.attempts, torch.cuda.get_device_name(0)))
+    if not args.skip_kernels:
+        kernels(say, 1024, 64, args.attempts, args.iters, args.warmup)
+    if not args.skip_rate:
+        for layout in args.layouts:
+            for budget in BUDGETS:
+                goal_rate(say, layout, budget, args.policies)
+
+
+if __name__ == '__main__':
+    main()
