@@ -9,6 +9,7 @@
 // block, the rarely needed EPA polytope lives in per-lane private memory.
 #pragma once
 #include "rv_dev_math.h"
+#include "rv_dev_wave.h"
 
 namespace rv {
 
@@ -66,30 +67,11 @@ struct DevMan {
 // Every lane of the group ends up with the same result.
 // Host emulation: the serial loop.
 #if RV_ON_DEVICE
-template <int N> RV_DEV float row_ror_f(float x) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x120 + N, 0xf, 0xf, false));
-}
-template <int N> RV_DEV int row_ror_i(int x) { return __builtin_amdgcn_update_dpp(0, x, 0x120 + N, 0xf, 0xf, false); }
 // two-stage reduction: the largest projection (4 DPP max steps), then the lowest lane
 // index that attains it (4 DPP min steps) -- exactly the serial first-maximum -- and one
 // broadcast LDS read of the winning vertex
-// (v_max_f32 on the rotated value: equal to the ternary for every finite input up to the sign of a zero,
-// which neither the index search `val == m` nor the uses of the projection can see)
-// (ONE instruction, v_max_f32_dpp, behind the two wait states a DPP read of a just-written VGPR needs.  Through
-// __builtin_fmaxf(update_dpp(0, x), x) a step was five issue slots: the move of the `old' operand, the wait state, the DPP
-// move, a v_max x, x that quiets a possible signalling NaN of the moved value, and the maximum itself)
-template <int N> RV_DEV float row_ror_fmax(float x) {
-  float r;
-  if (N == 8) asm("s_nop 1\n\tv_max_f32_dpp %0, %1, %1 row_ror:8 row_mask:0xf bank_mask:0xf" : "=v"(r) : "v"(x));
-  else if (N == 4) asm("s_nop 1\n\tv_max_f32_dpp %0, %1, %1 row_ror:4 row_mask:0xf bank_mask:0xf" : "=v"(r) : "v"(x));
-  else if (N == 2) asm("s_nop 1\n\tv_max_f32_dpp %0, %1, %1 row_ror:2 row_mask:0xf bank_mask:0xf" : "=v"(r) : "v"(x));
-  else asm("s_nop 1\n\tv_max_f32_dpp %0, %1, %1 row_ror:1 row_mask:0xf bank_mask:0xf" : "=v"(r) : "v"(x));
-  return r;
-}
-template <int N> RV_DEV int row_ror_imin(int x) {
-  int o = row_ror_i<N>(x);
-  return o < x ? o : x;
-}
+// (a max step is row_ror_fmax of rv_dev_wave.h, v_max_f32 on the rotated value: equal to the ternary for every finite
+// input up to the sign of a zero, which neither the index search `val == m` nor the uses of the projection can see)
 RV_DEV v3 support_v(const float* verts, int n, v3 d, float* proj, int* idx_out = nullptr) {
   const int sl = (int)threadIdx.x & 15;
   const int j = sl < n ? sl : n - 1;

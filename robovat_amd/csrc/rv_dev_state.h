@@ -1,5 +1,5 @@
 // rv_dev_state.h -- whole env states as data: save, restore, branch (rv_state_save / rv_state_load / rv_branch) and
-// the record of a simulated plan step (rv_plan_simulate).  Included by rv_kernels.hip only, after rv_dev_env.h.
+// the record of a simulated plan step (rv_plan_simulate).  Included by rv_kernels.hip only.
 //
 // A DevEnv block holds no pointer and no env id; every random draw of the env program is stateless Philox keyed by
 // (seed, global env id, stream, reset_count | macro_index), and an env.step() with given actions draws nothing.  The
@@ -12,6 +12,11 @@
 // (rv_env_kernel.h, rv_env_task: `k0 > 0`), and every later task sees what the launch itself stored.
 #ifndef RV_DEV_STATE_H_
 #define RV_DEV_STATE_H_
+#include "rv_dev_env_types.h"
+
+// (the kernels here are at file scope.  rv_kernels.hip, the only includer, says `using namespace rv` before it includes
+// this header; the include above and this declaration are what lets the header compile on its own)
+using rv::DevEnv;
 
 #define RV_STATE_TPB 256
 #define RV_STATE_WORDS ((int)(sizeof(DevEnv) / 4))

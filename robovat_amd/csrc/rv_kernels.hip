@@ -24,6 +24,7 @@
 #include <new>
 
 #include "../../include/rovat.h"
+#include "rv_dev_wave.h"
 #include "rv_dev_env.h"
 #include "rv_dev_obs.h"
 #include "rv_dev_grasp_sampler.h"
@@ -273,8 +274,6 @@ __global__ void k_obs_snap(const DevEnv* envs, int n, ObsSnap* snaps, const rv_s
   const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x); if (i >= n) return;
   obs_snap_fill(envs[i], &scene->arm, snaps[i]);
 }
-RV_DEV float wave_min(float x) { for (int o = 32; o > 0; o >>= 1) { float y = __shfl_xor(x, o); x = y < x ? y : x; } return x; }
-RV_DEV float wave_max(float x) { for (int o = 32; o > 0; o >>= 1) { float y = __shfl_xor(x, o); x = y > x ? y : x; } return x; }
 // SegmentedPointCloudObs (camera_obs.py:182-238): one wave per (observation, body); see rv_dev_obs.h
 __global__ __launch_bounds__(64) void k_point_cloud(const ObsSnap* snaps, int n_snaps, int n_envs, float* out,
                                                     const rv_config* c, const rv_scene* scene) {

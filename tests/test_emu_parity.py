@@ -26,7 +26,7 @@ def emu_library(arrangement='inline'):
     so = os.path.join(EMU_DIR, name)
     src = os.path.join(EMU_DIR, 'rv_emu.cpp')
     csrc = os.path.join(EMU_DIR, '..', '..', 'robovat_amd', 'csrc')
-    deps = [src, os.path.join(EMU_DIR, 'rv_emu_hooks.h')] + [os.path.join(csrc, n) for n in ('rv_dev_env.h', 'rv_dev_collide.h', 'rv_dev_math.h')]
+    deps = [src, os.path.join(EMU_DIR, 'rv_emu_hooks.h')] + [os.path.join(csrc, n) for n in sorted(os.listdir(csrc)) if n.endswith('.h')]
     if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
         subprocess.run(['g++'] + EMU_FLAGS + defines + [src, '-o', so], check=True)
     lib = C.CDLL(so)
