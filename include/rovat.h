@@ -33,7 +33,7 @@ extern "C" {
 #define RV_MAXH        4   /* convex hulls per shape (V-HACD parts)                */
 #define RV_MAXV       16   /* vertices per convex hull                             */
 #define RV_MAXP       28   /* faces per convex hull (2 V - 4 for V = 16)           */
-#define RV_PC_MAXPIX 2048  /* visible pixels of one body kept for point-cloud sampling (more: every stride-th one) */
+#define RV_PC_MAXPIX 2048  /* visible pixels of one body kept for point-cloud sampling (more: every stride-th one, or this many evenly spaced if num_points needs them) */
 #define RV_MAX_SHAPES 16   /* shape templates per scene                            */
 #define RV_NJ          9   /* arm joints: 7 limb (right_j0..j6) + 2 finger         */
 #define RV_NLIMB       7
@@ -798,7 +798,7 @@ int  rv_get_manifold_counts(rv_world* w, int32_t* d_out /* [N][RV_NMAN] */);
  *      camera_obs.py:182-238: ray-cast depth + segmentation, deprojection, P pixels per body
  *      emitted in the order of their Philox keys -- a random permutation, so the row order within
  *      a body's cloud carries no meaning; bodies with more than RV_PC_MAXPIX = 2048 visible pixels
- *      are sampled with a stride).  NULL pointers are skipped. */
+ *      are sampled with a stride, or from RV_PC_MAXPIX evenly spaced ones where the stride leaves fewer than P).  NULL pointers are skipped. */
 typedef struct rv_obs_buffers {
   float*   d_position;     /* [N][RV_MAXB][3]                                   */
   float*   d_body_mask;    /* [N][RV_MAXB]                                      */

@@ -3110,8 +3110,10 @@ void orc_point_cloud(orc_world* w, float* out) {
           const int v0 = (int)rclamp(R(floor)(mv) - R(1.0), R(0.0), H1), v1 = (int)rclamp(R(floor)(xv) + R(2.0), R(0.0), H1);
           const int ww = u1 - u0 + 1, hh = v1 - v0 + 1;
           const int total = (xu < R(0.0) || xv < R(0.0) || mu > W1 || mv > H1) ? 0 : ww * hh;
-          /* a body with more than RV_PC_MAXPIX visible pixels: every stride-th one (scan order) is kept */
-          int stride = 1;
+          /* a body with more than RV_PC_MAXPIX visible pixels: `num` of every `den` are kept, evenly spaced in scan order
+           * (rank r goes to slot r * num / den, the first rank of a slot stays): every stride-th pixel, or, where that would
+           * leave fewer than num_points asks for, RV_PC_MAXPIX of all */
+          unsigned num = 1u, den = 1u; int kept = 0;
           for (int pass = 0; pass < 2; ++pass) {
             n = 0;
             for (int idx = 0; idx < total; ++idx) {
@@ -3122,13 +3124,24 @@ void orc_point_cloud(orc_world* w, float* out) {
               if (!(who == b && d > (real)c->cam_near)) continue;
               pc_deproject(e, cam_o, (real)u, (real)v, d, pt);
               if (!pc_crop_ok(c, pt)) continue;
-              if (n % stride == 0 && n / stride < RV_PC_MAXPIX) { pix[n / stride] = ((uint32_t)v << 16) | (uint32_t)u; dep[n / stride] = d; }
+              int pos = n, keep = 1;
+              if (den > 1u) {
+                const unsigned long long rn = (unsigned long long)n * num;
+                pos = (int)(rn / den);
+                keep = rn - (unsigned long long)pos * den < (unsigned long long)num;
+              }
+              if (keep && pos < RV_PC_MAXPIX) { pix[pos] = ((uint32_t)v << 16) | (uint32_t)u; dep[pos] = d; }
               n++;
             }
             if (n <= RV_PC_MAXPIX) break;
-            if (pass == 0) stride = (n + RV_PC_MAXPIX - 1) / RV_PC_MAXPIX;
+            if (pass == 0) {
+              const int stride = (n + RV_PC_MAXPIX - 1) / RV_PC_MAXPIX;
+              kept = (n + stride - 1) / stride;
+              if (kept >= P) den = (unsigned)stride;
+              else { num = (unsigned)RV_PC_MAXPIX; den = (unsigned)n; kept = RV_PC_MAXPIX; }
+            }
           }
-          n = (n + stride - 1) / stride;
+          if (den > 1u) n = kept;
         }
       }
       if (n == 0) { for (int j = 0; j < P * 3; ++j) o[j] = 0.0f; continue; }

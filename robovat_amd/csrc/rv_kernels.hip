@@ -335,9 +335,11 @@ __global__ __launch_bounds__(64) void k_point_cloud(const ObsSnap* snaps, int n_
         }
         arm_mask = (unsigned)(__ballot(may) & 0x3ffull);
       }
-      // pass 0 keeps every visible pixel; a body with more than RV_PC_MAXPIX of them is cast again and every
-      // stride-th visible pixel (scan order) is kept, so that the sample covers the whole body
-      int stride = 1;
+      // pass 0 keeps every visible pixel; a body with more than RV_PC_MAXPIX of them is cast again and `num` of every
+      // `den` visible pixels are kept, evenly spaced in scan order (rank r goes to slot r * num / den, the first rank of
+      // a slot stays), so that the sample covers the whole body: every stride-th pixel, or, where that would leave
+      // fewer pixels than num_points asks for (they are between RV_PC_MAXPIX / 2 and RV_PC_MAXPIX), RV_PC_MAXPIX of all
+      unsigned num = 1u, den = 1u; int kept = 0;
       for (int pass = 0; pass < 2; ++pass) {
         n = 0;
         for (int base = 0; base < total; base += 64) {
@@ -351,14 +353,24 @@ __global__ __launch_bounds__(64) void k_point_cloud(const ObsSnap* snaps, int n_
           }
           const unsigned long long bal = __ballot(vis);
           const int rank = n + (int)__popcll(bal & ((1ull << lane) - 1ull));
-          const int pos = rank / stride;
-          if (vis && rank % stride == 0 && pos < RV_PC_MAXPIX) { s_pix[pos] = ((uint32_t)v << 16) | (uint32_t)u; s_dep[pos] = dep; }
+          int pos = rank; bool keep = true;
+          if (den > 1u) {
+            const unsigned long long rn = (unsigned long long)rank * num;
+            pos = (int)(rn / den);
+            keep = rn - (unsigned long long)pos * den < (unsigned long long)num;
+          }
+          if (vis && keep && pos < RV_PC_MAXPIX) { s_pix[pos] = ((uint32_t)v << 16) | (uint32_t)u; s_dep[pos] = dep; }
           n += (int)__popcll(bal);
         }
         if (n <= RV_PC_MAXPIX) break;
-        if (pass == 0) stride = (n + RV_PC_MAXPIX - 1) / RV_PC_MAXPIX;
+        if (pass == 0) {
+          const int stride = (n + RV_PC_MAXPIX - 1) / RV_PC_MAXPIX;
+          kept = (n + stride - 1) / stride;
+          if (kept >= P) den = (unsigned)stride;
+          else { num = (unsigned)RV_PC_MAXPIX; den = (unsigned)n; kept = RV_PC_MAXPIX; }
+        }
       }
-      n = (n + stride - 1) / stride;
+      if (den > 1u) n = kept;
     }
   }
   __syncthreads();
