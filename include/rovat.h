@@ -449,6 +449,33 @@ int  rv_policy_antipodal(rv_world* w, const float* d_depth, const rv_antipodal_p
 #define RV_AP_MAX_SAMPLES 64
 int  rv_policy_antipodal_multi(rv_world* w, const float* d_depth, const rv_antipodal_params* h_params, int32_t macro_index,
                                int32_t num_samples, float* d_image_grasps, float* d_actions4, int32_t* d_count, int32_t* d_status);
+/* ---- grasp-centred depth crops: what a grasp-quality model reads for each candidate.  The reference's
+ *      image_utils.transform (robovat/perception/image_utils.py:14-41: translate the grasp centre to the image centre,
+ *      rotate the grasp axis onto the image's x axis about (W/2, H/2), nearest neighbour, zero outside) followed by
+ *      image_utils.crop (:44-86) about the centre, for K image grasps per env in one launch.  With theta the angle of
+ *      p2 - p1 and g the midpoint of row (n, k), the image of that row is
+ *        crop(transform(depth[n], (H/2 - g_y, W/2 - g_x), theta), h*step, w*step)[step/2::step, step/2::step]
+ *      (step 1: the reference's two calls) wherever the (h*step) x (w*step) window lies inside the image; an output
+ *      pixel whose window position lies outside it is read from the source all the same (the reference composition
+ *      gives 0 there).  The arithmetic -- float32, unfused, a source coordinate rounded by floor(v + 0.5), inside
+ *      decided in float before any conversion -- is written out in csrc/rv_dev_grasp_sampler.h.  Agreement with
+ *      OpenCV's warpAffine on pixels whose source coordinate lies at a rounding boundary is unverified.  A NaN,
+ *      infinite or far-away row gives an all-zero image.  d_depth [N][H][W] (H, W from the params), d_grasps [N][K][5]
+ *      as rv_policy_antipodal_multi writes them, d_images [N][K][h][w], d_grasp_depths [N][K] (or NULL): column 4 of the
+ *      rows.  Any world, push or grasp: it supplies N, the device and the stream; no env is read or changed.
+ *      Asynchronous on the world's stream.  RV_ERR_VALUE, with every output left untouched: a NULL pointer other than
+ *      d_grasp_depths, a buffer that is not 4-byte aligned, height or width < 1, crop_height or crop_width outside
+ *      [1, RV_GC_MAX_SIDE], step outside [1, RV_GC_MAX_STEP], k outside [1, RV_AP_MAX_SAMPLES]. ---- */
+#define RV_GC_MAX_SIDE 256
+#define RV_GC_MAX_STEP 16
+typedef struct rv_grasp_crop_params {
+  int32_t height, width;            /* of the depth images */
+  int32_t crop_height, crop_width;  /* h, w of one output image, 1 .. RV_GC_MAX_SIDE */
+  int32_t step;                     /* 1 .. RV_GC_MAX_STEP: every step-th pixel of an (h*step) x (w*step) crop */
+  int32_t reserved[3];
+} rv_grasp_crop_params;
+int  rv_grasp_crops(rv_world* w, const rv_grasp_crop_params* h_params, const float* d_depth, const float* d_grasps, int32_t k,
+                    float* d_images, float* d_grasp_depths);
 
 /* ---- planning-mode PushReward: get_reward_fn(task, layout, is_planning=True) (push_reward.py:272-374 with the
  *      planning branches :110-151 insertion_termination, :168-200 crossing_termination, :230-238 check_stride,

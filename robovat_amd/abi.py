@@ -317,6 +317,24 @@ ANTIPODAL_API = {
 }
 
 
+RV_GC_MAX_SIDE = 256
+RV_GC_MAX_STEP = 16
+
+
+class rv_grasp_crop_params(C.Structure):
+    _fields_ = [
+        ('height', i32), ('width', i32), ('crop_height', i32), ('crop_width', i32), ('step', i32), ('reserved', i32 * 3),
+    ]
+
+
+# rv_grasp_crops (include/rovat.h): world, h_params, d_depth, d_grasps, k, d_images, d_grasp_depths; lib.load() binds it
+# from here
+GRASP_CROP_API = {
+    'rv_grasp_crops': (C.c_int, [C.c_void_p, C.POINTER(rv_grasp_crop_params), C.c_void_p, C.c_void_p, i32,
+                                 C.c_void_p, C.c_void_p]),
+}
+
+
 def bind_state_api(handle):
     """restype / argtypes of the STATE_API functions on a loaded librovat_hip.so"""
     for name, (res, args) in STATE_API.items():

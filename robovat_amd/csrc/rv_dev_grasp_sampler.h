@@ -78,6 +78,30 @@
 //    NumPy slicing would wrap or shrink);
 //  * more than RV_AP_MAX_EDGES edge pixels: status RV_AP_TOO_MANY_EDGES, never a silent truncation.
 //
+// Grasp-centred depth crops (rv_grasp_crops, k_grasp_crops): the input of a grasp-quality model for each
+// image grasp the sampler returned.  Reference: image_utils.transform (robovat/perception/image_utils.py:14-41) then
+// image_utils.crop (:44-86), with nearest-neighbour resampling and zero fill.  For row (n, k) = [x1, y1, x2, y2, depth]
+// and output pixel (i, j) of an h x w image sampled every `step` pixels, float32, every product and sum rounded on its own:
+//   ax = x2 - x1;  ay = y2 - y1;  len = sqrt(ax*ax + ay*ay)
+//   c, s = (len > 0 and finite) ? (ax/len, ay/len) : (1, 0)
+//   gx = 0.5*(x1 + x2);  gy = 0.5*(y1 + y2)
+//   x0 = floor(0.5*W - 0.5*(w*step)) - 0.5*W                 (y0 likewise with H, h)
+//   ox = x0 + (j*step + step/2)  (integer division)           oy = y0 + (i*step + step/2)
+//   sx = (c*ox - s*oy) + gx;      sy = (s*ox + c*oy) + gy
+//   inside = sx >= -0.5 && sx < W - 0.5 && sy >= -0.5 && sy < H - 0.5     (false for NaN)
+//   ix = min((int)floor(sx + 0.5), W - 1);  iy likewise
+//   out[i][j] = inside ? depth[n][iy][ix] : 0
+// `inside` is decided in float before anything becomes an integer, so a NaN, infinite or far-away row reads nothing and
+// gives zeros, and an index that is formed lies in [0, W-1] x [0, H-1].  OpenCV's warpAffine rounds its coordinates in
+// fixed point: agreement with it on pixels whose source coordinate lies at a rounding boundary is unverified.
+// Shape: no LDS, no atomics, no barrier.  A wave owns 64 P consecutive output pixels of ONE image (lane l the P pixels
+// from 64 P unit + P l on), so the grasp row is wave-uniform -- its address comes from a readfirstlane'd wave number and
+// the five floats arrive by scalar loads -- and a wave's stores are one contiguous run of 256 P bytes.  P = 4 (one
+// 16-byte store per lane) when h w is a multiple of 4 and at least 256 and the images are 16-byte aligned, else P = 1:
+// an 8 x 8 crop is one wave, and the four waves of a workgroup serve four images.  The reads are a gather inside a
+// window of at most sqrt(2) (side * step) pixels around the centre, served by the caches.  Every index is a size_t.
+// tests/grasp_crop_host.py restates this in float32 NumPy, operation for operation; the GPU tests compare bit for bit.
+//
 // Memory: the two filter passes go through a per-env slice [2][Hc][Wc] of a lazily grown world scratch
 // buffer (pass 1 in the first half, the filtered crop in the second; the resize reuses the first half).
 // The edge list (pixel, 4 B) and normals (float2, 8 B) live in LDS: RV_AP_MAX_EDGES = 4096 -> 48 KiB per
@@ -603,4 +627,70 @@ __global__ __launch_bounds__(RV_AP_TPB) void k_policy_antipodal_multi(const rv::
   const size_t row = (size_t)i * K + tid;
   for (int k = 0; k < 5; ++k) A.grasps[row * 5 + k] = g[k];
   if (A.actions4) for (int k = 0; k < 4; ++k) A.actions4[row * 4 + k] = a4[k];
+}
+
+// rv_grasp_crops (the header comment states the arithmetic and the shape)
+namespace rv {
+struct GcArgs {
+  const float* depth;       // [N][H][W]
+  const float* grasps;      // [rows][5]
+  float* images;            // [rows][h][w]
+  float* grasp_depths;      // [rows] or null
+  int H, W, h, w, step;
+  uint32_t units;           // waves per image: ceil(h w / (64 P))
+  uint32_t rows, K;         // N K, K
+};
+// the frame of one grasp row: centre, unit axis, and the crop window's first sample relative to the image centre
+struct GcFrame { float c, s, gx, gy, x0, y0; };
+RV_DEV GcFrame gc_frame(const GcArgs& a, const float* g) {
+  GcFrame f;
+  const float x1 = g[0], y1 = g[1], x2 = g[2], y2 = g[3];
+  const float ax = x2 - x1, ay = y2 - y1;
+  const float len = fsqrtr(ax * ax + ay * ay);
+  const bool ok = len > 0.0f && len <= 3.402823466e38f;
+  f.c = ok ? ax / len : 1.0f; f.s = ok ? ay / len : 0.0f;
+  f.gx = 0.5f * (x1 + x2); f.gy = 0.5f * (y1 + y2);
+  const float hw = 0.5f * (float)a.W, hh = 0.5f * (float)a.H;
+  f.x0 = ffloorr(hw - 0.5f * (float)(a.w * a.step)) - hw;
+  f.y0 = ffloorr(hh - 0.5f * (float)(a.h * a.step)) - hh;
+  return f;
+}
+RV_DEV float gc_pixel(const GcArgs& a, const GcFrame& f, const float* img, int i, int j) {
+  const float ox = f.x0 + (float)(j * a.step + a.step / 2), oy = f.y0 + (float)(i * a.step + a.step / 2);
+  const float sx = (f.c * ox - f.s * oy) + f.gx, sy = (f.s * ox + f.c * oy) + f.gy;
+  const bool inside = sx >= -0.5f && sx < (float)a.W - 0.5f && sy >= -0.5f && sy < (float)a.H - 0.5f;
+  if (!inside) return 0.0f;
+  int ix = (int)ffloorr(sx + 0.5f), iy = (int)ffloorr(sy + 0.5f);
+  ix = ix < a.W - 1 ? ix : a.W - 1; iy = iy < a.H - 1 ? iy : a.H - 1;
+  return img[(size_t)iy * (size_t)a.W + (size_t)ix];
+}
+}  // namespace rv
+
+template <int P>
+__global__ __launch_bounds__(256) void k_grasp_crops(rv::GcArgs a) {
+  using namespace rv;
+  const int lane = (int)threadIdx.x & 63;
+  const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4u + (threadIdx.x >> 6)));
+  const uint32_t row = wave / a.units, unit = wave - row * a.units;
+  if (row >= a.rows) return;
+  const float* g = a.grasps + (size_t)row * 5;
+  const GcFrame f = gc_frame(a, g);
+  const float* img = a.depth + (size_t)(row / a.K) * (size_t)a.H * (size_t)a.W;
+  float* out = a.images + (size_t)row * (size_t)a.h * (size_t)a.w;
+  if (unit == 0u && lane == 0 && a.grasp_depths) a.grasp_depths[row] = g[4];
+  const int total = a.h * a.w;
+  const int p0 = (int)unit * (64 * P) + lane * P;
+  if (p0 >= total) return;
+  int i = p0 / a.w, j = p0 - i * a.w;
+  if (P == 1) {
+    out[p0] = gc_pixel(a, f, img, i, j);
+  } else {
+    // (h w is a multiple of P here: the P pixels of a lane are all inside the image; they may span rows of it)
+    float v[P];
+    for (int q = 0; q < P; ++q) {
+      v[q] = gc_pixel(a, f, img, i, j);
+      if (++j == a.w) { j = 0; ++i; }
+    }
+    *reinterpret_cast<float4*>(out + p0) = make_float4(v[0], v[1], v[2], v[3]);
+  }
 }

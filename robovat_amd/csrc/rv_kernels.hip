@@ -10,6 +10,8 @@
 //   k_cem_refit     one workgroup per env: rank the returns, refit mean / std to the elites (rv_dev_cem.h)
 //   k_depth_noise_draw / k_depth_noise_apply   the depth sensor noise model: keyed per-image scalars and noise grid, then
 //                   gamma multiplier + bicubic upsampling staged in LDS, one lane per pixel (rv_dev_depth_noise.h)
+//   k_grasp_crops   grasp-centred depth crops per image grasp: a wave per 64 or 256 consecutive output pixels of one
+//                   image, the grasp row wave-uniform, a nearest-neighbour gather (rv_dev_grasp_sampler.h)
 //   k_*             small one-thread-per-env accessors behind the getters,
 //                   setters, observation, reward and policy entry points
 #include <hip/hip_runtime.h>
@@ -1325,6 +1327,36 @@ int rv_depth_noise(rv_world* w, const rv_depth_noise_params* h_params, const flo
   HIPCHK(hipGetLastError());
   if (v4) hipLaunchKernelGGL(k_depth_noise_apply<4>, dim3((unsigned)blocks), dim3(256), 0, w->stream, a, (int)tiles_x, (int)tiles_y);
   else hipLaunchKernelGGL(k_depth_noise_apply<1>, dim3((unsigned)blocks), dim3(256), 0, w->stream, a, (int)tiles_x, (int)tiles_y);
+  HIPCHK(hipGetLastError());
+  return RV_OK;
+}
+int rv_grasp_crops(rv_world* w, const rv_grasp_crop_params* h_params, const float* d_depth, const float* d_grasps, int32_t k,
+                   float* d_images, float* d_grasp_depths) {
+  WCHK(w);
+  if (!h_params) return fail(RV_ERR_VALUE, "rv_grasp_crops: null params");
+  NEED(d_depth, "rv_grasp_crops"); NEED(d_grasps, "rv_grasp_crops"); NEED(d_images, "rv_grasp_crops");
+  const rv_grasp_crop_params& p = *h_params;
+  if (!aligned_to(d_depth, 4) || !aligned_to(d_grasps, 4) || !aligned_to(d_images, 4) || !aligned_to(d_grasp_depths, 4))
+    return fail(RV_ERR_VALUE, "rv_grasp_crops: the buffers must be 4-byte aligned");
+  if (p.height < 1 || p.width < 1) return fail(RV_ERR_VALUE, "rv_grasp_crops: height or width < 1");
+  if (p.crop_height < 1 || p.crop_height > RV_GC_MAX_SIDE || p.crop_width < 1 || p.crop_width > RV_GC_MAX_SIDE)
+    return fail(RV_ERR_VALUE, "rv_grasp_crops: crop_height or crop_width outside [1, RV_GC_MAX_SIDE]");
+  if (p.step < 1 || p.step > RV_GC_MAX_STEP) return fail(RV_ERR_VALUE, "rv_grasp_crops: step outside [1, RV_GC_MAX_STEP]");
+  if (k < 1 || k > RV_AP_MAX_SAMPLES) return fail(RV_ERR_VALUE, "rv_grasp_crops: k outside [1, RV_AP_MAX_SAMPLES]");
+  const long long rows = (long long)w->n * k;
+  const int px = p.crop_height * p.crop_width;
+  // a wave owns 64 P consecutive pixels of one image: P = 4 (16-byte stores) when the images allow it
+  const bool v4 = px % 4 == 0 && px >= 256 && aligned_to(d_images, 16);
+  const int per_wave = v4 ? 256 : 64;
+  const long long units = (px + per_wave - 1) / per_wave, waves = rows * units;
+  if (rows > 0x7fffffffLL || waves > 0x7fffffffLL) return fail(RV_ERR_VALUE, "rv_grasp_crops: too many pixels for one launch");
+  GcArgs a;
+  a.depth = d_depth; a.grasps = d_grasps; a.images = d_images; a.grasp_depths = d_grasp_depths;
+  a.H = p.height; a.W = p.width; a.h = p.crop_height; a.w = p.crop_width; a.step = p.step;
+  a.units = (uint32_t)units; a.rows = (uint32_t)rows; a.K = (uint32_t)k;
+  const dim3 grid((unsigned)((waves + 3) / 4));
+  if (v4) hipLaunchKernelGGL(k_grasp_crops<4>, grid, dim3(256), 0, w->stream, a);
+  else hipLaunchKernelGGL(k_grasp_crops<1>, grid, dim3(256), 0, w->stream, a);
   HIPCHK(hipGetLastError());
   return RV_OK;
 }

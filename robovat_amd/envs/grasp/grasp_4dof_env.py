@@ -123,6 +123,42 @@ class VecGrasp4DofEnv(object):
         self.antipodal_image_grasps, self.antipodal_actions4 = g, a
         return a if self.config.ACTION.TYPE == 'CUBOID' else g
 
+    def grasp_images(self, image_grasps=None, depth=None, **crop):
+        """The input of a grasp-quality model for every candidate (rv_grasp_crops): the depth image
+        re-centred on the grasp, rotated so that the grasp axis is horizontal, and cropped.  ``image_grasps`` [N, K, 5] or
+        [N, 5] (None: ``antipodal_image_grasps`` of the last sampling call; ValueError if there was none); ``depth``
+        [N, H, W] (None: rendered now, without sensor noise); ``crop``: the fields of ``lib.grasp_crop_params``.
+        Returns (images float32 [N, K, h, w], grasp depths float32 [N, K]) on the device."""
+        from robovat_amd import lib
+        if image_grasps is None:
+            image_grasps = self.antipodal_image_grasps
+            if image_grasps is None:
+                raise ValueError('grasp_images: no image grasps given and no antipodal sampling call before this one')
+        if depth is None:
+            depth, _ = self.world.render()
+        return self.world.grasp_crops(depth, image_grasps, lib.grasp_crop_params(**crop))
+
+    def collect_grasp_samples(self, num_samples, depth=None, config=None, **crop):
+        """Labelled grasp samples of the envs as they are now: one depth image (``depth`` [N, H, W]; None: rendered once,
+        without sensor noise) goes to ``sample_antipodal_candidates(num_samples)`` and to ``grasp_images``, then
+        ``try_grasps(antipodal_actions4)`` executes every candidate on a copy of its env.  The envs themselves do not
+        change.  Returns a dict of device tensors: ``images`` [N, K, h, w], ``grasp_depths`` [N, K], ``image_grasps``
+        [N, K, 5], ``actions4`` [N, K, 4], ``rewards`` [N, K], ``dones`` uint8 [N, K], ``count`` int32 [N], ``status``
+        int32 [N] and ``valid`` bool [N, K] = status[n] == 1 and k < count[n].  Rows from ``count`` on repeat row 0 and an
+        env without a grasp carries its RandomPolicy draw: ``valid`` is how a consumer leaves them out."""
+        torch = self.world.torch
+        if depth is None:
+            depth, _ = self.world.render()
+        self.sample_antipodal_candidates(num_samples, depth=depth, config=config)
+        grasps, actions4 = self.antipodal_image_grasps, self.antipodal_actions4
+        count, status = self.antipodal_count, self.antipodal_status
+        images, grasp_depths = self.grasp_images(grasps, depth, **crop)
+        rewards, dones = self.try_grasps(actions4)
+        k = torch.arange(int(grasps.shape[1]), device=self.device, dtype=torch.int32)
+        valid = (status == 1)[:, None] & (k[None, :] < count[:, None])
+        return {'images': images, 'grasp_depths': grasp_depths, 'image_grasps': grasps, 'actions4': actions4,
+                'rewards': rewards, 'dones': dones, 'count': count, 'status': status, 'valid': valid}
+
     def save_state(self):
         """All N envs as they are now (``lib.World.save_state``): a ``lib.Snapshot`` on the device, plus the index of the
         env's next policy draw."""
@@ -269,6 +305,26 @@ class Grasp4DofEnv(object):
         if status != 1:
             raise ValueError('Failed to sample any valid grasp (antipodal status %d).' % status)
         return a[0].cpu().numpy()
+
+    def grasp_images(self, image_grasps=None, depth=None, **crop):
+        """Grasp-centred depth crops of this env's image: ``image_grasps`` [K, 5] or [5] (None: those of the last
+        sampling call; ValueError if there was none), ``depth`` [H, W] (None: rendered now).  Returns NumPy (images
+        [K, h, w], grasp depths [K])."""
+        if image_grasps is not None:
+            image_grasps = np.asarray(image_grasps, np.float32).reshape(1, -1, 5)
+        if depth is not None:
+            depth = np.asarray(depth, np.float32).reshape((1,) + np.shape(depth)[-2:])
+        images, depths = self._vec.grasp_images(image_grasps, depth, **crop)
+        return images[0].cpu().numpy(), depths[0].cpu().numpy()
+
+    def collect_grasp_samples(self, num_samples, depth=None, config=None, **crop):
+        """``VecGrasp4DofEnv.collect_grasp_samples`` for this env: the same dict as NumPy arrays without the env axis
+        (``images`` [K, h, w], ..., ``count`` and ``status`` scalars, ``valid`` [K]).  An env without a grasp is not an
+        error here: its ``valid`` is all False."""
+        if depth is not None:
+            depth = np.asarray(depth, np.float32).reshape((1,) + np.shape(depth)[-2:])
+        out = self._vec.collect_grasp_samples(num_samples, depth, config, **crop)
+        return {key: v[0].cpu().numpy() for key, v in out.items()}
 
     antipodal_status = property(lambda s: s._vec.antipodal_status)
     antipodal_count = property(lambda s: s._vec.antipodal_count)

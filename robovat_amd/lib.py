@@ -39,6 +39,7 @@ SYMBOLS = [
     'rv_depth_noise',
     'rv_policy_heuristic_multi', 'rv_plan_propose',
     'rv_get_route_field', 'rv_policy_route_multi', 'rv_plan_propose_route',
+    'rv_grasp_crops',
 ]
 
 _EXC = {abi.RV_ERR_VALUE: ValueError, abi.RV_ERR_STATE: RuntimeError,
@@ -182,7 +183,8 @@ def load():
                  'rv_query_contacts', 'rv_get_manifold_counts', 'rv_get_episode_returns'):
         getattr(lib, name).argtypes = [vp, vp]
     abi.bind_state_api(lib)
-    for api in (abi.ANTIPODAL_API, abi.CEM_API, abi.DEPTH_NOISE_API, abi.PUSH_PROPOSAL_API, abi.PUSH_ROUTE_API):
+    for api in (abi.ANTIPODAL_API, abi.CEM_API, abi.DEPTH_NOISE_API, abi.PUSH_PROPOSAL_API, abi.PUSH_ROUTE_API,
+                abi.GRASP_CROP_API):
         for name, (res, args) in api.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, list(args)
@@ -305,6 +307,20 @@ def depth_noise_params(config=None, **overrides):
     for k, v in overrides.items():
         if k not in names:
             raise TypeError('depth_noise_params: unknown field %r' % (k,))
+        setattr(p, k, type(getattr(p, k))(v))
+    return p
+
+
+def grasp_crop_params(crop_height=32, crop_width=32, step=3, **overrides):
+    """An ``rv_grasp_crop_params``: ``crop_height`` x ``crop_width`` output pixels, every ``step``-th pixel of a window of
+    ``step`` times that size around the grasp.  The defaults are BUILD-CHOSEN, not the reference's (its ``transform`` and
+    ``crop`` take their sizes from the caller): a 96-pixel window sampled to 32 x 32.  ``height`` / ``width`` start at 0
+    -- ``World.grasp_crops`` fills them in from the tensor -- and keyword arguments override fields by their C names."""
+    p = abi.rv_grasp_crop_params(height=0, width=0, crop_height=int(crop_height), crop_width=int(crop_width), step=int(step))
+    names = [n for n, _ in abi.rv_grasp_crop_params._fields_ if n != 'reserved']
+    for k, v in overrides.items():
+        if k not in names:
+            raise TypeError('grasp_crop_params: unknown field %r' % (k,))
         setattr(p, k, type(getattr(p, k))(v))
     return p
 
@@ -671,6 +687,38 @@ class World(object):
         check(self.lib.rv_depth_noise(self.h, C.byref(p), self._ptr(d), self._ptr(out), None if g is None else self._ptr(g),
                                       None if ap is None else self._ptr(ap), None if grid is None else self._ptr(grid)))
         return (out, g, ap, grid) if record else out
+
+    # -- grasp-centred depth crops (include/rovat.h: rv_grasp_crops)
+    def grasp_crops(self, depth, grasps, params, out=None, grasp_depths=True):
+        """rv_grasp_crops: for every image grasp of ``grasps`` ([N, K, 5], or [N, 5] for K = 1: x1, y1, x2, y2, depth) the
+        depth image of its env re-centred on the grasp, rotated so that the grasp axis is horizontal, and cropped to
+        ``params`` (``grasp_crop_params(...)``; its height and width are taken from the tensor).  ``depth``: float32
+        [N, H, W] on the device.  ``out``: None for a new tensor, or a contiguous float32 [N, K, h, w] tensor to write.
+        Returns (images [N, K, h, w], grasp depths [N, K] -- column 4 of the rows -- or None with ``grasp_depths=False``)."""
+        torch = self.torch
+        d = torch.as_tensor(depth, dtype=torch.float32, device=self.device)
+        if d.dim() != 3 or int(d.shape[0]) != self.n:
+            raise ValueError('grasp_crops: depth must be [N, H, W] with N = %d, got %s' % (self.n, tuple(d.shape)))
+        g = torch.as_tensor(grasps, dtype=torch.float32, device=self.device)
+        if g.dim() == 2:
+            g = g[:, None, :]
+        if g.dim() != 3 or int(g.shape[0]) != self.n or int(g.shape[2]) != 5:
+            raise ValueError('grasp_crops: grasps must be [N, K, 5] or [N, 5] with N = %d, got %s' % (self.n, tuple(g.shape)))
+        d, g = d.contiguous(), g.contiguous()
+        k = int(g.shape[1])
+        p = abi.rv_grasp_crop_params.from_buffer_copy(params)
+        p.height, p.width = int(d.shape[1]), int(d.shape[2])
+        side = lambda v: min(max(int(v), 1), abi.RV_GC_MAX_SIDE)      # (the library refuses a size outside its range)
+        shape = (self.n, min(max(k, 1), abi.RV_AP_MAX_SAMPLES), side(p.crop_height), side(p.crop_width))
+        if out is None:
+            out = self._new(shape, torch.float32)
+        elif not (torch.is_tensor(out) and out.dtype == torch.float32 and out.device == d.device
+                  and tuple(out.shape) == (self.n, k, int(p.crop_height), int(p.crop_width)) and out.is_contiguous()):
+            raise ValueError('grasp_crops: out must be a contiguous float32 [N, K, h, w] tensor on the depth\'s device')
+        gd = self._new((self.n, shape[1]), torch.float32) if grasp_depths else None
+        check(self.lib.rv_grasp_crops(self.h, C.byref(p), self._ptr(d), self._ptr(g), k, self._ptr(out),
+                                      None if gd is None else self._ptr(gd)))
+        return out, gd
 
     # -- env states as data (include/rovat.h: rv_state_* / rv_branch / rv_plan_simulate)
     def state_bytes(self):

@@ -9,6 +9,11 @@ are keyed Philox blocks instead, and ``VecGrasp4DofEnv`` applies that one when `
 reference's ``scipy.misc.imresize(..., interp='bicubic', mode='F')`` called -- restated in float32 (Pillow keeps its
 weights and running sums in float64; the difference is a few units in the last place of the largest grid value).
 
+``transform`` and ``crop`` are the reference's ``image_utils`` pair that its ``depth_utils`` re-exports: translate and
+rotate an image with nearest-neighbour resampling, and cut a window out of it with zero fill.  Together they make the
+grasp-centred image a grasp-quality model reads; the batched version on the device is ``lib.World.grasp_crops``
+(``rv_grasp_crops``).
+
 ``inpaint`` is NOT part of this module: it fills the holes of a real sensor's image, runs a data-dependent number of
 iterations, and its final resize in the reference goes through an 8-bit image.
 """
@@ -57,6 +62,62 @@ def resize_bicubic(grid, factor):
         raise ValueError('resize_bicubic: grid must be [h, w], got %s' % (g.shape,))
     rows = _resize_axis(g, int(factor))
     return np.ascontiguousarray(_resize_axis(np.ascontiguousarray(rows.T), int(factor)).T)
+
+
+def transform(data, translation, theta):
+    """The reference's ``image_utils.transform`` (``robovat/perception/image_utils.py:14-41``, re-exported by its
+    ``depth_utils``): a new image [H, W] (or [H, W, C]) of the same dtype, ``data`` translated by ``translation`` = (row
+    shift, column shift) and then rotated by ``theta`` radians (positive = counter-clockwise) about ``(W/2, H/2)``,
+    resampled with nearest neighbour, zero outside.  Float64, defined by the inverse map: destination pixel ``(x, y)``
+    reads source ``(W/2 - tx, H/2 - ty) + [[cos, -sin], [sin, cos]] (x - W/2, y - H/2)``, each coordinate rounded by
+    ``floor(v + 0.5)``.  The reference calls ``cv2.warpAffine(..., INTER_NEAREST)``, which rounds its coordinates in fixed
+    point; OpenCV is not available to compare with, so agreement with it on pixels whose source coordinate lies at a
+    rounding boundary is UNVERIFIED.  The batched version on the device is ``lib.World.grasp_crops``."""
+    data = np.asarray(data)
+    if data.ndim not in (2, 3):
+        raise ValueError('transform: expected an image [H, W] or [H, W, C], got %s' % (data.shape,))
+    height, width = data.shape[0], data.shape[1]
+    ty, tx = float(translation[0]), float(translation[1])
+    c, s = np.cos(float(theta)), np.sin(float(theta))
+    y, x = np.meshgrid(np.arange(height, dtype=np.float64), np.arange(width, dtype=np.float64), indexing='ij')
+    ox, oy = x - width / 2.0, y - height / 2.0
+    sx = (width / 2.0 - tx) + (c * ox - s * oy)
+    sy = (height / 2.0 - ty) + (s * ox + c * oy)
+    ix, iy = np.floor(sx + 0.5), np.floor(sy + 0.5)
+    inside = (ix >= 0) & (ix < width) & (iy >= 0) & (iy < height)
+    ix = np.where(inside, ix, 0).astype(np.int64)
+    iy = np.where(inside, iy, 0).astype(np.int64)
+    out = data[iy, ix]
+    out[~inside] = 0
+    return out.astype(data.dtype)
+
+
+def crop(data, height, width, c0=None, c1=None):
+    """The reference's ``image_utils.crop`` (``robovat/perception/image_utils.py:44-86``): the ``height`` x ``width``
+    window of ``data`` [H, W] (or [H, W, C]) centred on row ``c0`` and column ``c1`` (None: the image centre), rows
+    ``floor(c0 - height / 2)`` to ``floor(c0 + height / 2)`` and columns likewise, zero where the window leaves the image
+    (what PIL's ``crop`` does); same dtype.  ValueError when the two floors do not span ``height`` x ``width``, as there."""
+    data = np.asarray(data)
+    if data.ndim not in (2, 3):
+        raise ValueError('crop: expected an image [H, W] or [H, W, C], got %s' % (data.shape,))
+    height = int(np.round(height))
+    width = int(np.round(width))
+    if c0 is None:
+        c0 = float(data.shape[0]) / 2
+    if c1 is None:
+        c1 = float(data.shape[1]) / 2
+    r0 = int(np.floor(c0 - float(height) / 2))
+    r1 = int(np.floor(c0 + float(height) / 2))
+    q0 = int(np.floor(c1 - float(width) / 2))
+    q1 = int(np.floor(c1 + float(width) / 2))
+    if r1 - r0 != height or q1 - q0 != width:
+        raise ValueError('Crop dims are incorrect.')
+    out = np.zeros((height, width) + data.shape[2:], data.dtype)
+    a0, a1 = max(r0, 0), min(r1, data.shape[0])
+    b0, b1 = max(q0, 0), min(q1, data.shape[1])
+    if a1 > a0 and b1 > b0:
+        out[a0 - r0:a1 - r0, b0 - q0:b1 - q0] = data[a0:a1, b0:b1]
+    return out
 
 
 def threshold_gradients(data, threshold):

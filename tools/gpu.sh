@@ -26,6 +26,9 @@
 #                  HeuristicShootingPushPolicy next to the other planners
 #   push_route     tools/push_route_bench.py: rv_policy_route_multi against a torch restatement, and the goal rate of
 #                  RouteShootingPushPolicy next to the other planners on crossing layouts 0 to 2; the kernels' resources
+#   grasp_crops    tools/grasp_crops_bench.py: rv_grasp_crops against a device copy and a torch restatement, and
+#                  collect_grasp_samples in samples per second; then the kernel's own duration from a profiler run of the
+#                  same tool, and its resources
 #   lanes          SQ_THREAD_CYCLES_VALU / SQ_ACTIVE_INST_VALU lane-utilisation pass (headline and no-deactivation)
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}; TAG=$1; shift
 O=$R/gpurun_out/$TAG; mkdir -p $O; cd $R
@@ -85,6 +88,14 @@ for STAGE in "$@"; do
       echo "depth_noise rc=$?" >> $O/time.txt
       grep -h "Name\|depth_noise" $(find $O/depth_noise_prof -name '*kernel_stats.csv') > $O/depth_noise_kernel_stats.txt
       tail -12 $O/depth_noise_bench.txt; cat $O/depth_noise_kernel_stats.txt ;;
+    grasp_crops)
+      timeout -k 10 900 python tools/grasp_crops_bench.py --out $O/grasp_crops_bench.txt > $O/grasp_crops_bench.log 2>&1 &&
+        timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $O/grasp_crops_prof -o gc --output-format csv -- python tools/grasp_crops_bench.py --skip-samples --iters 10 --warmup 2 > $O/grasp_crops_prof.log 2>&1
+      echo "grasp_crops rc=$?" >> $O/time.txt
+      grep -h "Name\|grasp_crops" $(find $O/grasp_crops_prof -name '*kernel_stats.csv') > $O/grasp_crops_kernel_stats.txt
+      python tools/kernel_resources.py > $O/kernel_resources_all.txt 2>&1
+      grep -h "^kernel\|grasp_crops" $O/kernel_resources_all.txt > $O/grasp_crops_kernel_resources.txt
+      tail -20 $O/grasp_crops_bench.txt; cat $O/grasp_crops_kernel_stats.txt ;;
     lanes)
       cd /tmp
       for V in head nd; do
