@@ -476,6 +476,36 @@ typedef struct rv_grasp_crop_params {
 } rv_grasp_crop_params;
 int  rv_grasp_crops(rv_world* w, const rv_grasp_crop_params* h_params, const float* d_depth, const float* d_grasps, int32_t k,
                     float* d_images, float* d_grasp_depths);
+/* ---- grasp-quality network: one logit per candidate from its crop (rv_grasp_crops) and its grasp depth, so that K
+ *      candidates can be ranked without executing them.  It replaces the choice of the reference's
+ *      AntipodalGrasp4DofPolicy (robovat/policies/grasp_policy.py:60-73), which takes sample(depth, intrinsics, 1) --
+ *      the first candidate -- as it comes.  Fixed topology, sizes in the descriptor (BUILD-CHOSEN, the reference has no
+ *      such model):
+ *        a = (x - im_mean) * im_inv_std;  u = (z - z_mean) * z_inv_std
+ *        c1 = pool2(relu(conv5x5_same(a; 1 -> c1)));  c2 = pool2(relu(conv3x3_same(c1; c1 -> c2)))
+ *        f1 = relu(fc(flatten(c2) -> f1));  p = relu(fc(u -> p));  f2 = relu(fc(concat(f1, p) -> f2));  logit = fc(f2 -> 1)
+ *      The output is the logit (no exponential on the device; a probability is sigmoid(logit)).  The arithmetic -- one
+ *      float32 FMA chain per dot product, from the bias, in ascending input index -- and the layout of the weight blob
+ *      are written out in csrc/rv_dev_grasp_quality.h.  Ranges: height and width multiples of 4 in
+ *      [RV_GQ_MIN_SIDE, RV_GQ_MAX_SIDE]; c1 and c2 multiples of 4 in [4, RV_GQ_MAX_CHANNELS]; f1 and f2 multiples of 4 in
+ *      [4, RV_GQ_MAX_FEATURES]; p a multiple of 4 in [4, RV_GQ_MAX_POSE]; reserved 0.  The default model is 32 x 32,
+ *      c1 = c2 = 16, f1 = f2 = 64, p = 16 (73 617 floats); the smallest is 8 x 8 with 4 everywhere.
+ *      rv_grasp_quality_weight_count: floats in the blob of such a model, or -1 for a NULL or refused descriptor.
+ *      rv_grasp_quality: d_weights the blob, d_images [N][k][height][width], d_grasp_depths [N][k], d_logits [N][k].
+ *      Stateless: any world, it supplies N, the device and the stream; no env is read or changed.  Asynchronous on the
+ *      world's stream.  RV_ERR_VALUE before any launch, with d_logits left untouched: a NULL pointer, a buffer that is not
+ *      4-byte aligned, a size outside its range, k outside [1, RV_AP_MAX_SAMPLES], a normalisation constant that is not
+ *      finite. ---- */
+#define RV_GQ_MIN_SIDE 8
+#define RV_GQ_MAX_SIDE 32
+#define RV_GQ_MAX_CHANNELS 16
+#define RV_GQ_MAX_FEATURES 128
+#define RV_GQ_MAX_POSE 32
+typedef struct rv_grasp_quality_model { int32_t height, width, c1, c2, f1, f2, p, reserved;
+                                        float im_mean, im_inv_std, z_mean, z_inv_std; } rv_grasp_quality_model;
+int64_t rv_grasp_quality_weight_count(const rv_grasp_quality_model* h_model);
+int  rv_grasp_quality(rv_world* w, const rv_grasp_quality_model* h_model, const float* d_weights,
+                      const float* d_images, const float* d_grasp_depths, int32_t k, float* d_logits);
 
 /* ---- planning-mode PushReward: get_reward_fn(task, layout, is_planning=True) (push_reward.py:272-374 with the
  *      planning branches :110-151 insertion_termination, :168-200 crossing_termination, :230-238 check_stride,

@@ -335,6 +335,29 @@ GRASP_CROP_API = {
 }
 
 
+RV_GQ_MIN_SIDE = 8
+RV_GQ_MAX_SIDE = 32
+RV_GQ_MAX_CHANNELS = 16
+RV_GQ_MAX_FEATURES = 128
+RV_GQ_MAX_POSE = 32
+
+
+class rv_grasp_quality_model(C.Structure):
+    _fields_ = [
+        ('height', i32), ('width', i32), ('c1', i32), ('c2', i32), ('f1', i32), ('f2', i32), ('p', i32), ('reserved', i32),
+        ('im_mean', C.c_float), ('im_inv_std', C.c_float), ('z_mean', C.c_float), ('z_inv_std', C.c_float),
+    ]
+
+
+# rv_grasp_quality_weight_count: h_model; rv_grasp_quality: world, h_model, d_weights, d_images, d_grasp_depths, k,
+# d_logits (include/rovat.h); lib.load() binds them from here
+GRASP_QUALITY_API = {
+    'rv_grasp_quality_weight_count': (C.c_int64, [C.POINTER(rv_grasp_quality_model)]),
+    'rv_grasp_quality': (C.c_int, [C.c_void_p, C.POINTER(rv_grasp_quality_model), C.c_void_p, C.c_void_p, C.c_void_p, i32,
+                                   C.c_void_p]),
+}
+
+
 def bind_state_api(handle):
     """restype / argtypes of the STATE_API functions on a loaded librovat_hip.so"""
     for name, (res, args) in STATE_API.items():

@@ -12,6 +12,8 @@
 //                   gamma multiplier + bicubic upsampling staged in LDS, one lane per pixel (rv_dev_depth_noise.h)
 //   k_grasp_crops   grasp-centred depth crops per image grasp: a wave per 64 or 256 consecutive output pixels of one
 //                   image, the grasp row wave-uniform, a nearest-neighbour gather (rv_dev_grasp_sampler.h)
+//   k_grasp_quality the grasp-quality network: a workgroup per 8 crops, activations in LDS, conv2 / fc1 / fc2 on the
+//                   f32 MFMA, conv1 / pose / logit as FMA chains on the VALU (rv_dev_grasp_quality.h)
 //   k_*             small one-thread-per-env accessors behind the getters,
 //                   setters, observation, reward and policy entry points
 #include <hip/hip_runtime.h>
@@ -30,6 +32,7 @@
 #include "rv_dev_env.h"
 #include "rv_dev_obs.h"
 #include "rv_dev_grasp_sampler.h"
+#include "rv_dev_grasp_quality.h"
 #include "rv_dev_contacts.h"
 #include "rv_dev_plan.h"
 #include "rv_dev_cem.h"
@@ -1357,6 +1360,48 @@ int rv_grasp_crops(rv_world* w, const rv_grasp_crop_params* h_params, const floa
   const dim3 grid((unsigned)((waves + 3) / 4));
   if (v4) hipLaunchKernelGGL(k_grasp_crops<4>, grid, dim3(256), 0, w->stream, a);
   else hipLaunchKernelGGL(k_grasp_crops<1>, grid, dim3(256), 0, w->stream, a);
+  HIPCHK(hipGetLastError());
+  return RV_OK;
+}
+static bool gq_model_ok(const rv_grasp_quality_model& m) {
+  const auto side = [](int v) { return v >= RV_GQ_MIN_SIDE && v <= RV_GQ_MAX_SIDE && v % 4 == 0; };
+  const auto mult4 = [](int v, int hi) { return v >= 4 && v <= hi && v % 4 == 0; };
+  return side(m.height) && side(m.width) && mult4(m.c1, RV_GQ_MAX_CHANNELS) && mult4(m.c2, RV_GQ_MAX_CHANNELS) &&
+         mult4(m.f1, RV_GQ_MAX_FEATURES) && mult4(m.f2, RV_GQ_MAX_FEATURES) && mult4(m.p, RV_GQ_MAX_POSE) && m.reserved == 0;
+}
+int64_t rv_grasp_quality_weight_count(const rv_grasp_quality_model* h_model) {
+  if (!h_model || !gq_model_ok(*h_model)) return -1;
+  const rv_grasp_quality_model& m = *h_model;
+  return (int64_t)gq_layout(m.height, m.width, m.c1, m.c2, m.f1, m.f2, m.p).count;
+}
+int rv_grasp_quality(rv_world* w, const rv_grasp_quality_model* h_model, const float* d_weights,
+                     const float* d_images, const float* d_grasp_depths, int32_t k, float* d_logits) {
+  WCHK(w);
+  if (!h_model) return fail(RV_ERR_VALUE, "rv_grasp_quality: null model");
+  NEED(d_weights, "rv_grasp_quality"); NEED(d_images, "rv_grasp_quality"); NEED(d_grasp_depths, "rv_grasp_quality");
+  NEED(d_logits, "rv_grasp_quality");
+  const rv_grasp_quality_model& m = *h_model;
+  if (!aligned_to(d_weights, 4) || !aligned_to(d_images, 4) || !aligned_to(d_grasp_depths, 4) || !aligned_to(d_logits, 4))
+    return fail(RV_ERR_VALUE, "rv_grasp_quality: the buffers must be 4-byte aligned");
+  if (!gq_model_ok(m)) return fail(RV_ERR_VALUE, "rv_grasp_quality: a size of the model is outside its range");
+  const float big = 3.402823466e38f;
+  const auto finite = [big](float v) { return v >= -big && v <= big; };
+  if (!finite(m.im_mean) || !finite(m.im_inv_std) || !finite(m.z_mean) || !finite(m.z_inv_std))
+    return fail(RV_ERR_VALUE, "rv_grasp_quality: a normalisation constant is not finite");
+  if (k < 1 || k > RV_AP_MAX_SAMPLES) return fail(RV_ERR_VALUE, "rv_grasp_quality: k outside [1, RV_AP_MAX_SAMPLES]");
+  const long long rows = (long long)w->n * k;
+  if (rows > 0x7fffffffLL) return fail(RV_ERR_VALUE, "rv_grasp_quality: too many samples for one launch");
+  const GqLayout L = gq_layout(m.height, m.width, m.c1, m.c2, m.f1, m.f2, m.p);
+  const size_t lds = (size_t)L.l_floats * sizeof(float);
+  // (more than the 64 KB a kernel gets unasked; 78 KB for the largest model, two workgroups per CU)
+  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_grasp_quality), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  GqArgs a;
+  a.images = d_images; a.depths = d_grasp_depths; a.logits = d_logits;
+  a.h = m.height; a.w = m.width; a.c1 = m.c1; a.c2 = m.c2; a.f1 = m.f1; a.f2 = m.f2; a.p = m.p;
+  a.im_mean = m.im_mean; a.im_inv_std = m.im_inv_std; a.z_mean = m.z_mean; a.z_inv_std = m.z_inv_std;
+  a.rows = (uint32_t)rows;
+  const dim3 grid((unsigned)((rows + RV_GQ_BATCH - 1) / RV_GQ_BATCH));
+  hipLaunchKernelGGL(k_grasp_quality, grid, dim3(RV_GQ_TPB), lds, w->stream, a, d_weights);
   HIPCHK(hipGetLastError());
   return RV_OK;
 }

@@ -138,6 +138,15 @@ class VecGrasp4DofEnv(object):
             depth, _ = self.world.render()
         return self.world.grasp_crops(depth, image_grasps, lib.grasp_crop_params(**crop))
 
+    def grasp_qualities(self, model, image_grasps=None, depth=None, **crop):
+        """The logits of a grasp-quality model for every candidate (rv_grasp_quality): ``grasp_images`` with
+        the model's height x width (``crop`` may give ``step``, default 3), then ``World.grasp_quality``.  ``model``: a
+        ``perception.grasp_quality.GraspQualityModel``; ``image_grasps`` and ``depth`` as in ``grasp_images`` (None: the
+        last sampling call's grasps, a render made now).  Returns float32 [N, K] on the device; the envs do not change."""
+        crop = dict(crop, crop_height=model.sizes['height'], crop_width=model.sizes['width'])
+        images, grasp_depths = self.grasp_images(image_grasps, depth, **crop)
+        return self.world.grasp_quality(images, grasp_depths, model)
+
     def collect_grasp_samples(self, num_samples, depth=None, config=None, **crop):
         """Labelled grasp samples of the envs as they are now: one depth image (``depth`` [N, H, W]; None: rendered once,
         without sensor noise) goes to ``sample_antipodal_candidates(num_samples)`` and to ``grasp_images``, then
@@ -316,6 +325,15 @@ class Grasp4DofEnv(object):
             depth = np.asarray(depth, np.float32).reshape((1,) + np.shape(depth)[-2:])
         images, depths = self._vec.grasp_images(image_grasps, depth, **crop)
         return images[0].cpu().numpy(), depths[0].cpu().numpy()
+
+    def grasp_qualities(self, model, image_grasps=None, depth=None, **crop):
+        """``VecGrasp4DofEnv.grasp_qualities`` for this env: ``image_grasps`` [K, 5] or [5] (None: those of the last
+        sampling call), ``depth`` [H, W] (None: rendered now).  Returns NumPy logits [K]."""
+        if image_grasps is not None:
+            image_grasps = np.asarray(image_grasps, np.float32).reshape(1, -1, 5)
+        if depth is not None:
+            depth = np.asarray(depth, np.float32).reshape((1,) + np.shape(depth)[-2:])
+        return self._vec.grasp_qualities(model, image_grasps, depth, **crop)[0].cpu().numpy()
 
     def collect_grasp_samples(self, num_samples, depth=None, config=None, **crop):
         """``VecGrasp4DofEnv.collect_grasp_samples`` for this env: the same dict as NumPy arrays without the env axis

@@ -40,6 +40,7 @@ SYMBOLS = [
     'rv_policy_heuristic_multi', 'rv_plan_propose',
     'rv_get_route_field', 'rv_policy_route_multi', 'rv_plan_propose_route',
     'rv_grasp_crops',
+    'rv_grasp_quality_weight_count', 'rv_grasp_quality',
 ]
 
 _EXC = {abi.RV_ERR_VALUE: ValueError, abi.RV_ERR_STATE: RuntimeError,
@@ -184,7 +185,7 @@ def load():
         getattr(lib, name).argtypes = [vp, vp]
     abi.bind_state_api(lib)
     for api in (abi.ANTIPODAL_API, abi.CEM_API, abi.DEPTH_NOISE_API, abi.PUSH_PROPOSAL_API, abi.PUSH_ROUTE_API,
-                abi.GRASP_CROP_API):
+                abi.GRASP_CROP_API, abi.GRASP_QUALITY_API):
         for name, (res, args) in api.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, list(args)
@@ -719,6 +720,45 @@ class World(object):
         check(self.lib.rv_grasp_crops(self.h, C.byref(p), self._ptr(d), self._ptr(g), k, self._ptr(out),
                                       None if gd is None else self._ptr(gd)))
         return out, gd
+
+    # -- grasp-quality network (include/rovat.h: rv_grasp_quality)
+    def grasp_quality(self, images, grasp_depths, model, out=None):
+        """rv_grasp_quality: the logit of ``model`` (a ``perception.grasp_quality.GraspQualityModel``) for every crop.
+        ``images``: float32 [N, K, h, w] with the model's h x w (or [N, h, w] for K = 1), as ``grasp_crops`` returns them;
+        ``grasp_depths``: float32 [N, K] (or [N]); ``out``: None for a new tensor, or a contiguous float32 [N, K] tensor
+        to write.  Returns the logits [N, K] (``torch.sigmoid`` makes probabilities of them).  The model's weight blob is
+        uploaded once per model object and device and kept on the model."""
+        torch = self.torch
+        x = torch.as_tensor(images, dtype=torch.float32, device=self.device)
+        if x.dim() == 3:
+            x = x[:, None]
+        h, w = int(model.sizes['height']), int(model.sizes['width'])
+        if x.dim() != 4 or int(x.shape[0]) != self.n or tuple(x.shape[2:]) != (h, w):
+            raise ValueError('grasp_quality: images must be [N, K, %d, %d] with N = %d, got %s' % (h, w, self.n, tuple(x.shape)))
+        k = int(x.shape[1])
+        z = torch.as_tensor(grasp_depths, dtype=torch.float32, device=self.device)
+        if z.dim() == 1:
+            z = z[:, None]
+        if tuple(z.shape) != (self.n, k):
+            raise ValueError('grasp_quality: grasp_depths must be [N, K] = [%d, %d], got %s' % (self.n, k, tuple(z.shape)))
+        x, z = x.contiguous(), z.contiguous()
+        if out is None:
+            out = self._new((self.n, min(max(k, 1), abi.RV_AP_MAX_SAMPLES)), torch.float32)
+        elif not (torch.is_tensor(out) and out.dtype == torch.float32 and out.device == x.device
+                  and tuple(out.shape) == (self.n, k) and out.is_contiguous()):
+            raise ValueError('grasp_quality: out must be a contiguous float32 [N, K] tensor on the images\' device')
+        key = str(self.device)
+        blob = model._device_blobs.get(key)
+        if blob is None:
+            desc = model.descriptor()
+            count = int(self.lib.rv_grasp_quality_weight_count(C.byref(desc)))
+            host = model.blob()
+            if count != host.size:
+                raise ValueError('grasp_quality: the library wants %d weights for this model, blob() has %d' % (count, host.size))
+            blob = model._device_blobs[key] = torch.from_numpy(host).to(self.device)
+        desc = model.descriptor()
+        check(self.lib.rv_grasp_quality(self.h, C.byref(desc), self._ptr(blob), self._ptr(x), self._ptr(z), k, self._ptr(out)))
+        return out
 
     # -- env states as data (include/rovat.h: rv_state_* / rv_branch / rv_plan_simulate)
     def state_bytes(self):

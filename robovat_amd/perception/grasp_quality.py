@@ -1,0 +1,208 @@
+"""The grasp-quality network of rv_grasp_quality (include/rovat.h) on the host side: its descriptor and its
+weights as named float32 arrays in torch's natural layouts, the weight blob in the kernel's layout, an ``nn.Module`` of
+the same network for training, and the way back from a trained module.
+
+    a = (x - im_mean) * im_inv_std;  u = (z - z_mean) * z_inv_std
+    c1 = pool2(relu(conv5x5_same(a; 1 -> c1)));  c2 = pool2(relu(conv3x3_same(c1; c1 -> c2)))
+    f1 = relu(fc(flatten(c2) -> f1));  p = relu(fc(u -> p));  f2 = relu(fc(concat(f1, p) -> f2));  logit = fc(f2 -> 1)
+
+The output is a logit; ``torch.sigmoid`` makes a probability of it."""
+import numpy as np
+
+from robovat_amd import abi
+
+SIZE_NAMES = ('height', 'width', 'c1', 'c2', 'f1', 'f2', 'p')
+NORM_NAMES = ('im_mean', 'im_inv_std', 'z_mean', 'z_inv_std')
+# BUILD-CHOSEN: 32 x 32 is the default of lib.grasp_crop_params
+DEFAULT_SIZES = dict(height=32, width=32, c1=16, c2=16, f1=64, f2=64, p=16)
+# the smallest model the library takes
+TINY_SIZES = dict(height=8, width=8, c1=4, c2=4, f1=4, f2=4, p=4)
+PARAM_NAMES = ('conv1.weight', 'conv1.bias', 'conv2.weight', 'conv2.bias', 'fc1.weight', 'fc1.bias',
+               'pose.weight', 'pose.bias', 'fc2.weight', 'fc2.bias', 'out.weight', 'out.bias')
+
+
+def param_shapes(height, width, c1, c2, f1, f2, p):
+    """name -> shape of every parameter, torch's natural layouts"""
+    k1 = c2 * (height // 4) * (width // 4)
+    return {'conv1.weight': (c1, 1, 5, 5), 'conv1.bias': (c1,), 'conv2.weight': (c2, c1, 3, 3), 'conv2.bias': (c2,),
+            'fc1.weight': (f1, k1), 'fc1.bias': (f1,), 'pose.weight': (p, 1), 'pose.bias': (p,),
+            'fc2.weight': (f2, f1 + p), 'fc2.bias': (f2,), 'out.weight': (1, f2), 'out.bias': (1,)}
+
+
+def check_sizes(sizes):
+    """ValueError unless the sizes lie in the ranges include/rovat.h states"""
+    def mult4(v, lo, hi):
+        return lo <= v <= hi and v % 4 == 0
+    ok = (mult4(sizes['height'], abi.RV_GQ_MIN_SIDE, abi.RV_GQ_MAX_SIDE) and mult4(sizes['width'], abi.RV_GQ_MIN_SIDE, abi.RV_GQ_MAX_SIDE)
+          and mult4(sizes['c1'], 4, abi.RV_GQ_MAX_CHANNELS) and mult4(sizes['c2'], 4, abi.RV_GQ_MAX_CHANNELS)
+          and mult4(sizes['f1'], 4, abi.RV_GQ_MAX_FEATURES) and mult4(sizes['f2'], 4, abi.RV_GQ_MAX_FEATURES)
+          and mult4(sizes['p'], 4, abi.RV_GQ_MAX_POSE))
+    if not ok:
+        raise ValueError('GraspQualityModel: a size is outside its range (include/rovat.h): %r' % (sizes,))
+
+
+class GraspQualityModel(object):
+    """Descriptor + weights.  ``sizes``: height, width, c1, c2, f1, f2, p; ``norm``: im_mean, im_inv_std, z_mean, z_inv_std
+    (kept as float32); ``params``: name -> float32 array (``PARAM_NAMES``, ``param_shapes``).  The arrays are taken as
+    frozen once the model has been used on a device: ``World.grasp_quality`` uploads ``blob()`` once per model object and
+    device (call ``touch()`` after changing an array in place)."""
+
+    def __init__(self, params, norm=None, **sizes):
+        self.sizes = dict(DEFAULT_SIZES)
+        for k, v in sizes.items():
+            if k not in SIZE_NAMES:
+                raise TypeError('GraspQualityModel: unknown size %r' % (k,))
+            self.sizes[k] = int(v)
+        check_sizes(self.sizes)
+        self.norm = {'im_mean': np.float32(0), 'im_inv_std': np.float32(1), 'z_mean': np.float32(0), 'z_inv_std': np.float32(1)}
+        for k, v in (norm or {}).items():
+            if k not in NORM_NAMES:
+                raise TypeError('GraspQualityModel: unknown normalisation constant %r' % (k,))
+            self.norm[k] = np.float32(v)
+        shapes = param_shapes(**self.sizes)
+        if sorted(params) != sorted(PARAM_NAMES):
+            raise ValueError('GraspQualityModel: params must have exactly the names %r' % (PARAM_NAMES,))
+        self.params = {}
+        for name in PARAM_NAMES:
+            arr = np.ascontiguousarray(np.asarray(params[name], np.float32))
+            if arr.shape != shapes[name]:
+                raise ValueError('GraspQualityModel: %s must be %r, got %r' % (name, shapes[name], arr.shape))
+            self.params[name] = arr
+        self._device_blobs = {}
+
+    def touch(self):
+        """forget the uploaded blobs (after an in-place change of ``params``)"""
+        self._device_blobs = {}
+
+    @classmethod
+    def random_init(cls, seed, norm=None, **sizes):
+        """Uniform(-1/sqrt(fan_in), 1/sqrt(fan_in)) weights and biases (torch's default for these layers) from
+        ``np.random.RandomState(seed)``, drawn in ``PARAM_NAMES`` order."""
+        full = dict(DEFAULT_SIZES)
+        for k, v in sizes.items():
+            if k not in SIZE_NAMES:
+                raise TypeError('GraspQualityModel: unknown size %r' % (k,))
+            full[k] = int(v)
+        check_sizes(full)
+        shapes = param_shapes(**full)
+        rng = np.random.RandomState(seed)
+        params = {}
+        for name in PARAM_NAMES:
+            layer = name.split('.')[0]
+            fan_in = int(np.prod(shapes[layer + '.weight'][1:]))
+            bound = 1.0 / np.sqrt(fan_in)
+            params[name] = rng.uniform(-bound, bound, size=shapes[name]).astype(np.float32)
+        return cls(params, norm, **full)
+
+    def descriptor(self):
+        """the ``abi.rv_grasp_quality_model`` of this model"""
+        return abi.rv_grasp_quality_model(reserved=0, **dict(self.sizes, **{k: float(v) for k, v in self.norm.items()}))
+
+    def weight_count(self):
+        """floats in ``blob()`` (what rv_grasp_quality_weight_count returns for the descriptor)"""
+        return int(sum(int(np.prod(s)) for s in param_shapes(**self.sizes).values()))
+
+    def blob(self):
+        """The weights in the order and layout the kernel reads (csrc/rv_dev_grasp_quality.h): conv1 as it is, conv2 and
+        the fc layers K-major (transposed, so that consecutive outputs are consecutive floats), every bias after its
+        weights."""
+        s, q = self.sizes, self.params
+        parts = [q['conv1.weight'].reshape(s['c1'], 25), q['conv1.bias'],
+                 q['conv2.weight'].reshape(s['c2'], 9 * s['c1']).T, q['conv2.bias'],
+                 q['fc1.weight'].T, q['fc1.bias'], q['pose.weight'].reshape(s['p']), q['pose.bias'],
+                 q['fc2.weight'].T, q['fc2.bias'], q['out.weight'].reshape(s['f2']), q['out.bias']]
+        out = np.concatenate([np.ascontiguousarray(a, np.float32).ravel() for a in parts])
+        assert out.size == self.weight_count()
+        return out
+
+    def save(self, path):
+        """one ``.npz``: the sizes, the normalisation constants and every parameter under its name"""
+        data = {'sizes': np.array([self.sizes[k] for k in SIZE_NAMES], np.int32),
+                'norm': np.array([self.norm[k] for k in NORM_NAMES], np.float32)}
+        data.update(self.params)
+        with open(path, 'wb') as f:
+            np.savez(f, **data)
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path) as z:
+            sizes = {k: int(v) for k, v in zip(SIZE_NAMES, z['sizes'])}
+            norm = {k: np.float32(v) for k, v in zip(NORM_NAMES, z['norm'])}
+            params = {name: z[name] for name in PARAM_NAMES}
+        return cls(params, norm, **sizes)
+
+    def torch_module(self):
+        """An ``nn.Module`` of the same network carrying these weights (float32), for training and for comparison:
+        ``forward(images [B, h, w], grasp_depths [B]) -> logits [B]``."""
+        import torch
+        m = module_class()(norm=self.norm, **self.sizes)
+        with torch.no_grad():
+            state = m.state_dict()
+            for name in PARAM_NAMES:
+                state[name].copy_(torch.from_numpy(self.params[name]))
+        return m
+
+    @classmethod
+    def from_torch_module(cls, module, norm=None):
+        """The model of a ``GraspQualityModule`` (its own normalisation constants unless ``norm`` gives others)."""
+        state = module.state_dict()
+        params = {name: state[name].detach().cpu().numpy().astype(np.float32) for name in PARAM_NAMES}
+        own = {k: np.float32(float(state[k].item())) for k in NORM_NAMES}
+        own.update(norm or {})
+        return cls(params, own, **module.sizes)
+
+
+_MODULE = None
+
+
+def module_class():
+    """``GraspQualityModule`` (made on first use: torch is not imported with this file)"""
+    global _MODULE
+    if _MODULE is None:
+        _MODULE = _module_class()
+    return _MODULE
+
+
+def _module_class():
+    import torch
+    from torch import nn
+    import torch.nn.functional as F
+
+    class GraspQualityModule(nn.Module):
+        __doc__ = """The network in torch (``F.conv2d`` with zero padding, ``max_pool2d``, ``linear``); the normalisation
+        constants are float32 buffers."""
+
+        def __init__(self, norm=None, **sizes):
+            super(GraspQualityModule, self).__init__()
+            full = dict(DEFAULT_SIZES)
+            full.update({k: int(v) for k, v in sizes.items()})
+            check_sizes(full)
+            self.sizes = full
+            s = full
+            self.conv1 = nn.Conv2d(1, s['c1'], 5, padding=2)
+            self.conv2 = nn.Conv2d(s['c1'], s['c2'], 3, padding=1)
+            self.fc1 = nn.Linear(s['c2'] * (s['height'] // 4) * (s['width'] // 4), s['f1'])
+            self.pose = nn.Linear(1, s['p'])
+            self.fc2 = nn.Linear(s['f1'] + s['p'], s['f2'])
+            self.out = nn.Linear(s['f2'], 1)
+            norm = dict({'im_mean': 0.0, 'im_inv_std': 1.0, 'z_mean': 0.0, 'z_inv_std': 1.0}, **(norm or {}))
+            for k in NORM_NAMES:
+                self.register_buffer(k, torch.tensor(float(np.float32(norm[k])), dtype=torch.float32))
+
+        def forward(self, images, grasp_depths):
+            a = ((images - self.im_mean) * self.im_inv_std)[:, None]
+            u = ((grasp_depths - self.z_mean) * self.z_inv_std)[:, None]
+            c1 = F.max_pool2d(F.relu(F.conv2d(a, self.conv1.weight, self.conv1.bias, padding=2)), 2)
+            c2 = F.max_pool2d(F.relu(F.conv2d(c1, self.conv2.weight, self.conv2.bias, padding=1)), 2)
+            f1 = F.relu(F.linear(c2.flatten(1), self.fc1.weight, self.fc1.bias))
+            p = F.relu(F.linear(u, self.pose.weight, self.pose.bias))
+            f2 = F.relu(F.linear(torch.cat([f1, p], dim=1), self.fc2.weight, self.fc2.bias))
+            return F.linear(f2, self.out.weight, self.out.bias)[:, 0]
+
+    return GraspQualityModule
+
+
+def __getattr__(name):
+    if name == 'GraspQualityModule':
+        return module_class()
+    raise AttributeError(name)

@@ -100,6 +100,57 @@ class LookaheadGrasp4DofPolicy(Policy):
         return actions
 
 
+class GraspQualityPolicy(Policy):
+    """AntipodalGrasp4DofPolicy with a learned ranking in place of "the first one": ``num_samples`` distinct antipodal
+    grasps per env (``sample_antipodal_candidates``) from one depth image, their grasp-centred crops and the logits of
+    ``model`` (``grasp_qualities``: rv_grasp_crops, rv_grasp_quality), and the action is the candidate with the highest
+    logit among the rows the sampler found (``antipodal_status == 1`` and k < ``antipodal_count``), the lowest index among
+    equals; candidate 0 -- the grasp AntipodalGrasp4DofPolicy takes -- where an env has no such row or its best logit is
+    NaN.  Nothing is executed: no ``try_grasps``, no ground-truth state, one render.  The action is in the env's
+    ACTION.TYPE.  Kept: ``last_choice`` [N] and ``last_logits`` [N, K].  ``model``: a
+    ``perception.grasp_quality.GraspQualityModel``; ``crop``: ``step`` of the crops (default 3).  ``env``: a
+    ``VecGrasp4DofEnv`` or a ``Grasp4DofEnv``."""
+
+    def __init__(self, env, model, num_samples, config=None, **crop):
+        config = config or configs.AttrDict(configs.ANTIPODAL_GRASP_4DOF_POLICY_CONFIG)
+        super(GraspQualityPolicy, self).__init__(env, config)
+        self._vec = getattr(env, '_vec', env)      # (a Grasp4DofEnv is a VecGrasp4DofEnv of one)
+        self._single = self._vec is not env
+        if not hasattr(self._vec, 'grasp_qualities'):
+            raise NotImplementedError('GraspQualityPolicy needs a Grasp4DofEnv / VecGrasp4DofEnv')
+        self.model, self.crop = model, dict(crop)
+        self.num_samples = int(num_samples)
+        if self.num_samples < 1:
+            raise ValueError('GraspQualityPolicy: num_samples must be positive')
+        self.last_choice = self.last_logits = None
+
+    def _action(self, observation):
+        v = self._vec
+        t = v.world.torch
+        depth = None if observation is None else observation.get('depth')
+        if depth is not None and self._single:
+            depth = np.asarray(depth, np.float32).reshape((1,) + np.shape(depth)[-2:])
+        if depth is None:
+            depth, _ = v.world.render()      # (one render serves the sampler and the crops)
+        cand = v.sample_antipodal_candidates(self.num_samples, depth, self.config)
+        if self._single and int(v.antipodal_status[0].item()) != 1:
+            raise ValueError('Failed to sample any valid grasp (antipodal status %d).' % int(v.antipodal_status[0].item()))
+        logits = v.grasp_qualities(self.model, v.antipodal_image_grasps, depth, **self.crop)
+        k = self.num_samples
+        index = t.arange(k, device=v.device)[None, :].expand(v.num_envs, k)
+        valid = (v.antipodal_status == 1)[:, None] & (index < v.antipodal_count[:, None])
+        masked = t.where(valid, logits, t.full_like(logits, float('-inf')))
+        best = masked.max(dim=1, keepdim=True).values      # (NaN if a valid logit is NaN; -inf without a valid row)
+        first = t.where(valid & (masked == best), index, t.full_like(index, k)).min(dim=1).values
+        choice = t.where(first < k, first, t.zeros_like(first))      # (NaN equals nothing: candidate 0)
+        self.last_choice, self.last_logits = choice, logits
+        actions = cand[t.arange(v.num_envs, device=v.device), choice]
+        if self._single:
+            self.last_choice, self.last_logits = int(choice[0]), logits[0].cpu().numpy()
+            return actions[0].cpu().numpy()
+        return actions
+
+
 class ShootingPushPolicy(Policy):
     """Random-shooting model-predictive control with the simulator as the model: per env ``num_samples`` candidate
     action sequences of ``horizon`` steps, drawn U(-1, 1) from a torch generator seeded with ``seed``, are tried on

@@ -29,6 +29,9 @@
 #   grasp_crops    tools/grasp_crops_bench.py: rv_grasp_crops against a device copy and a torch restatement, and
 #                  collect_grasp_samples in samples per second; then the kernel's own duration from a profiler run of the
 #                  same tool, and its resources
+#   grasp_quality  tools/grasp_quality_bench.py: rv_grasp_quality against torch's eager forward and the f32 matrix peak, and
+#                  the success rate of GraspQualityPolicy next to candidate 0 and the look-ahead; then the kernel's own
+#                  duration from a profiler run of the kernel half, and its resources
 #   lanes          SQ_THREAD_CYCLES_VALU / SQ_ACTIVE_INST_VALU lane-utilisation pass (headline and no-deactivation)
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}; TAG=$1; shift
 O=$R/gpurun_out/$TAG; mkdir -p $O; cd $R
@@ -96,6 +99,14 @@ for STAGE in "$@"; do
       python tools/kernel_resources.py > $O/kernel_resources_all.txt 2>&1
       grep -h "^kernel\|grasp_crops" $O/kernel_resources_all.txt > $O/grasp_crops_kernel_resources.txt
       tail -20 $O/grasp_crops_bench.txt; cat $O/grasp_crops_kernel_stats.txt ;;
+    grasp_quality)
+      timeout -k 10 1100 python tools/grasp_quality_bench.py --out $O/grasp_quality_bench.txt > $O/grasp_quality_bench.log 2>&1 &&
+        timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $O/grasp_quality_prof -o gq --output-format csv -- python tools/grasp_quality_bench.py --skip-policy --skip-torch --iters 10 --warmup 2 > $O/grasp_quality_prof.log 2>&1
+      echo "grasp_quality rc=$?" >> $O/time.txt
+      grep -h "Name\|grasp_quality" $(find $O/grasp_quality_prof -name '*kernel_stats.csv') > $O/grasp_quality_kernel_stats.txt
+      python tools/kernel_resources.py > $O/kernel_resources_all.txt 2>&1
+      grep -h "^kernel\|grasp_quality" $O/kernel_resources_all.txt > $O/grasp_quality_kernel_resources.txt
+      tail -30 $O/grasp_quality_bench.txt; cat $O/grasp_quality_kernel_stats.txt ;;
     lanes)
       cd /tmp
       for V in head nd; do
