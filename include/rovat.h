@@ -506,6 +506,52 @@ typedef struct rv_grasp_quality_model { int32_t height, width, c1, c2, f1, f2, p
 int64_t rv_grasp_quality_weight_count(const rv_grasp_quality_model* h_model);
 int  rv_grasp_quality(rv_world* w, const rv_grasp_quality_model* h_model, const float* d_weights,
                       const float* d_images, const float* d_grasp_depths, int32_t k, float* d_logits);
+/* ---- cross-entropy refinement of grasp candidates: the step between two scorings (score, keep the elites, resample
+ *      around them, score again -- how a grasp-quality network is normally used; with try_grasps rewards as scores, an
+ *      evolutionary search with the simulator as the model).  One launch per iteration; the arithmetic, operation for
+ *      operation, is in csrc/rv_dev_grasp_refine.h.
+ *      d_depth [N][H][W] (H, W from the params); d_grasps [N][k][5] as rv_policy_antipodal_multi or an earlier call of
+ *      this function wrote them; d_scores [N][k] logits or rewards; d_count, d_status [N] the sampler's outputs, either
+ *      may be NULL: input row j of env n is a CANDIDATE when (no d_status or status[n] == RV_AP_OK) and (no d_count or
+ *      j < count[n]).  V = the env's candidates, ranked in the total order of rv_cem_refit (descending, the lower index
+ *      first among equals, +0 == -0, NaNs last and by index); E' = min(n_elites, V).
+ *      d_grasps_out [N][k][5] (must not be d_grasps): V = 0: the k rows copied bit for bit.  Otherwise rows 0 .. E'-1 are
+ *      the elites in rank order, bit for bit (their crops and logits are the same next round: an env's best score never
+ *      goes down), and row j >= E' is a child of elite r = (j - E') mod E', [x1, y1, x2, y2, z]: with g = 0.5 (p1 + p2),
+ *      a = 0.5 (p2 - p1) and four standard normals z0 .. z3 (Box-Muller of rv_dev_cem.h, |z| <= 5.77) the child has
+ *      centre g + sigma_center (z0, z1), half axis a rotated by sigma_angle z2, and depth z + sigma_depth z3 clamped to
+ *      [cd + MIN_DEPTH_OFFSET, cd + MAX_DEPTH_OFFSET], cd the child's own centre-depth window minimum.  It is accepted
+ *      when its centre (of the row as written) lies inside the crop, passes the sampler's step 8 on the unfiltered
+ *      image (distance from the crop boundary >= MIN_DIST_FROM_BOUNDARY; cd neither 0 nor NaN) and its five floats are
+ *      finite; else the row is its parent's, bit for bit.  Antipodality is not re-checked.
+ *      d_parent [N][k] (or NULL): the input index of the parent for an elite and an accepted child, -1 - parent for a
+ *      child that fell back; j itself where V = 0.  d_count_out [N] (or NULL): k where V > 0, else 0.
+ *      d_actions4_out [N][k][4] (or NULL): ap_grasp_4dof of output row j with the env's own calibration, the conversion
+ *      of rv_policy_antipodal_multi; it needs a grasp world.  Without it any world will do, as with rv_grasp_crops: it
+ *      supplies N, the global env ids, the seed, the device and the stream.
+ *      h_sampler supplies use_crop, crop, min_dist_from_boundary, depth_sample_window_height / _width, min_depth_offset
+ *      and max_depth_offset, nothing else (but all of it is checked as rv_policy_antipodal_multi checks it).
+ *      Draws: Philox keyed by the world's seed, the GLOBAL env id, macro_index in [0, 2^24), iteration in [0, 2^26), the
+ *      params' seed, the output row and the component -- not by N, k or n_elites; a key space of its own.
+ *      No env state is read beyond the id and the calibration, none is changed.  Asynchronous on the world's stream.
+ *      RV_ERR_VALUE before any launch, with every output untouched: a NULL required pointer, a buffer that is not
+ *      4-byte aligned, d_grasps_out == d_grasps, k outside [1, RV_AP_MAX_SAMPLES], n_elites outside [1, k], height or
+ *      width < 1, a sigma that is negative or not finite, macro_index or iteration outside its range, a nonzero reserved
+ *      word, sampler parameters that rv_policy_antipodal_multi would refuse, d_actions4_out on a push world. ---- */
+typedef struct rv_grasp_refine_params {
+  int32_t height, width;        /* of the depth images                                          */
+  int32_t macro_index, iteration; /* Philox: the env.step() being chosen, the refinement round  */
+  uint32_t seed;                /* the policy's seed, on top of the world's                     */
+  int32_t n_elites;             /* E in [1, k]                                                  */
+  float   sigma_center;         /* px,  >= 0, finite                                            */
+  float   sigma_angle;          /* rad, >= 0, finite                                            */
+  float   sigma_depth;          /* m,   >= 0, finite                                            */
+  int32_t reserved[3];
+} rv_grasp_refine_params;
+int  rv_grasp_refine(rv_world* w, const rv_grasp_refine_params* h_params, const rv_antipodal_params* h_sampler,
+                     const float* d_depth, const float* d_grasps, const float* d_scores, const int32_t* d_count,
+                     const int32_t* d_status, int32_t k, float* d_grasps_out, float* d_actions4_out,
+                     int32_t* d_parent, int32_t* d_count_out);
 
 /* ---- planning-mode PushReward: get_reward_fn(task, layout, is_planning=True) (push_reward.py:272-374 with the
  *      planning branches :110-151 insertion_termination, :168-200 crossing_termination, :230-238 check_stride,

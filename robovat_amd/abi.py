@@ -358,6 +358,26 @@ GRASP_QUALITY_API = {
 }
 
 
+RV_GR_MAX_ITERATION = 1 << 26
+RV_GR_MAX_MACRO_INDEX = 1 << 24
+
+
+class rv_grasp_refine_params(C.Structure):
+    _fields_ = [
+        ('height', i32), ('width', i32), ('macro_index', i32), ('iteration', i32), ('seed', C.c_uint32), ('n_elites', i32),
+        ('sigma_center', C.c_float), ('sigma_angle', C.c_float), ('sigma_depth', C.c_float), ('reserved', i32 * 3),
+    ]
+
+
+# rv_grasp_refine (include/rovat.h): world, h_params, h_sampler, d_depth, d_grasps, d_scores, d_count, d_status, k,
+# d_grasps_out, d_actions4_out, d_parent, d_count_out; lib.load() binds it from here
+GRASP_REFINE_API = {
+    'rv_grasp_refine': (C.c_int, [C.c_void_p, C.POINTER(rv_grasp_refine_params), C.POINTER(rv_antipodal_params),
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, i32,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
+
 def bind_state_api(handle):
     """restype / argtypes of the STATE_API functions on a loaded librovat_hip.so"""
     for name, (res, args) in STATE_API.items():

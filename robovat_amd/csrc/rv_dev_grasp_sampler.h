@@ -188,21 +188,11 @@ RV_DEV uint32_t ap_key(const rv_config* c, uint32_t gid, uint32_t word3, uint32_
 RV_DEV uint32_t ap_pix(uint32_t e, int rate, int r0, int c0, int W) {
   return (uint32_t)((r0 + rate * (int)(e >> 16)) * W + c0 + rate * (int)(e & 0xffffu));
 }
-// Step 8 for the ordered pair (a, b): force closure, distance from the crop boundary, the centre depth window.
-RV_DEV bool ap_check(const ApShared& s, const ApArgs& A, const float* img, int a, int b, float* center_depth) {
+// Step 8 without the force closure, for a centre (gx, gy) in full-image pixels: distance from the crop boundary, the
+// centre depth window.  (Shared with k_grasp_refine, rv_dev_grasp_refine.h, whose centres are not half-integers and
+// which admits only centres inside the crop: an int is formed from gx - WW, gx + WW, gy - WH and gy + WH.)
+RV_DEV bool ap_check_center(const ApArgs& A, const float* img, float gx, float gy, float* center_depth) {
   const rv_antipodal_params& p = A.p;
-  const int rate = p.downsample_rate;
-  const uint32_t ea = s.pix[a], eb = s.pix[b];
-  const int ra = rate * (int)(ea >> 16), ca = rate * (int)(ea & 0xffffu);
-  const int rb = rate * (int)(eb >> 16), cb = rate * (int)(eb & 0xffffu);
-  const float vr0 = (float)(rb - ra), vc0 = (float)(cb - ca);
-  const float len = sqrtf(vr0 * vr0 + vc0 * vc0);
-  const float vr = vr0 / len, vc = vc0 / len;
-  const float2 na = s.nrm[a], nb = s.nrm[b];
-  const float d1 = -(na.x * vr + na.y * vc), d2 = nb.x * vr + nb.y * vc;
-  if (!(d1 > p.cone_cos && d1 <= 1.0f && d2 > p.cone_cos && d2 <= 1.0f)) return false;
-  // centre in full-image pixels (half-integers: exact)
-  const float gx = 0.5f * (float)(ca + cb + 2 * A.c0), gy = 0.5f * (float)(ra + rb + 2 * A.r0);
   const float r1 = (float)(A.r0 + A.Hc), c1 = (float)(A.c0 + A.Wc);
   float dist = fabsf((float)A.r0 - gy);
   dist = fminf(dist, fabsf((float)A.c0 - gx)); dist = fminf(dist, fabsf(gy - r1)); dist = fminf(dist, fabsf(gx - c1));
@@ -220,6 +210,23 @@ RV_DEV bool ap_check(const ApShared& s, const ApArgs& A, const float* img, int a
   if (nan || mn == 0.0f || y1 <= y0 || x1w <= x0) return false;
   *center_depth = mn;
   return true;
+}
+// Step 8 for the ordered pair (a, b): force closure, then ap_check_center.
+RV_DEV bool ap_check(const ApShared& s, const ApArgs& A, const float* img, int a, int b, float* center_depth) {
+  const rv_antipodal_params& p = A.p;
+  const int rate = p.downsample_rate;
+  const uint32_t ea = s.pix[a], eb = s.pix[b];
+  const int ra = rate * (int)(ea >> 16), ca = rate * (int)(ea & 0xffffu);
+  const int rb = rate * (int)(eb >> 16), cb = rate * (int)(eb & 0xffffu);
+  const float vr0 = (float)(rb - ra), vc0 = (float)(cb - ca);
+  const float len = sqrtf(vr0 * vr0 + vc0 * vc0);
+  const float vr = vr0 / len, vc = vc0 / len;
+  const float2 na = s.nrm[a], nb = s.nrm[b];
+  const float d1 = -(na.x * vr + na.y * vc), d2 = nb.x * vr + nb.y * vc;
+  if (!(d1 > p.cone_cos && d1 <= 1.0f && d2 > p.cone_cos && d2 <= 1.0f)) return false;
+  // centre in full-image pixels (half-integers: exact)
+  const float gx = 0.5f * (float)(ca + cb + 2 * A.c0), gy = 0.5f * (float)(ra + rb + 2 * A.r0);
+  return ap_check_center(A, img, gx, gy, center_depth);
 }
 
 // Grasp2D.from_vector(g).as_4dof() (grasp_2d.py) in float32 with the env's calibration:

@@ -33,6 +33,7 @@
 #include "rv_dev_obs.h"
 #include "rv_dev_grasp_sampler.h"
 #include "rv_dev_grasp_quality.h"
+#include "rv_dev_grasp_refine.h"
 #include "rv_dev_contacts.h"
 #include "rv_dev_plan.h"
 #include "rv_dev_cem.h"
@@ -1159,12 +1160,8 @@ int rv_render(rv_world* w, float* d_depth, uint8_t* d_segmask) {
   HIPCHK(hipGetLastError());
   return RV_OK;
 }
-// the checks and the launch arguments the two antipodal entry points share (`fn`: the entry point the message names)
-static int antipodal_args(rv_world* w, const float* d_depth, const rv_antipodal_params* h_params, int32_t macro_index,
-                          const std::string& fn, ApArgs* out) {
-  const rv_antipodal_params& p = *h_params;
-  if (w->cfg.env_type != RV_ENV_GRASP) return fail(RV_ERR_VALUE, fn + ": a Grasp4DofEnv world only");
-  const int H = w->cfg.cam_height, W = w->cfg.cam_width;
+// the checks of the sampler's parameters against an H x W image, and the geometry they give (rv_grasp_refine shares them)
+static int antipodal_geometry(const rv_antipodal_params& p, int H, int W, const std::string& fn, ApArgs* out) {
   if (p.downsample_rate < 1 || p.downsample_rate > 8) return fail(RV_ERR_VALUE, fn + ": DOWNSAMPLE_RATE must be an integer in 1..8");
   if (p.depth_samples_per_grasp != 1) return fail(RV_ERR_VALUE, fn + ": DEPTH_SAMPLES_PER_GRASP must be 1 (one depth per grasp)");
   if (p.max_rejection_samples < 1) return fail(RV_ERR_VALUE, fn + ": MAX_REJECTION_SAMPLES must be positive");
@@ -1181,13 +1178,23 @@ static int antipodal_args(rv_world* w, const float* d_depth, const rv_antipodal_
   a.p = p; a.H = H; a.W = W; a.r0 = r0; a.c0 = c0; a.Hc = r1 - r0; a.Wc = c1 - c0;
   a.Hd = a.Hc / p.downsample_rate; a.Wd = a.Wc / p.downsample_rate;
   if (a.Hd < 2 || a.Wd < 2) return fail(RV_ERR_VALUE, fn + ": the downsampled crop must be at least 2 x 2");
+  *out = a;
+  return RV_OK;
+}
+// the checks and the launch arguments the two antipodal entry points share (`fn`: the entry point the message names)
+static int antipodal_args(rv_world* w, const float* d_depth, const rv_antipodal_params* h_params, int32_t macro_index,
+                          const std::string& fn, ApArgs* out) {
+  if (w->cfg.env_type != RV_ENV_GRASP) return fail(RV_ERR_VALUE, fn + ": a Grasp4DofEnv world only");
+  const int H = w->cfg.cam_height, W = w->cfg.cam_width;
+  ApArgs a;
+  int rc = antipodal_geometry(*h_params, H, W, fn, &a); if (rc != RV_OK) return rc;
   a.macro_index = macro_index;
   if (!d_depth) {
     int rc = ensure_floats(w, &w->d_ap_depth, &w->ap_depth_cap, (size_t)w->n * H * W); if (rc != RV_OK) return rc;
     rc = rv_render(w, w->d_ap_depth, nullptr); if (rc != RV_OK) return rc;
     d_depth = w->d_ap_depth;
   }
-  int rc = ensure_floats(w, &w->d_ap_scratch, &w->ap_scratch_cap, (size_t)w->n * 2 * a.Hc * a.Wc); if (rc != RV_OK) return rc;
+  rc = ensure_floats(w, &w->d_ap_scratch, &w->ap_scratch_cap, (size_t)w->n * 2 * a.Hc * a.Wc); if (rc != RV_OK) return rc;
   a.depth = d_depth; a.scratch = w->d_ap_scratch;
   *out = a;
   return RV_OK;
@@ -1402,6 +1409,42 @@ int rv_grasp_quality(rv_world* w, const rv_grasp_quality_model* h_model, const f
   a.rows = (uint32_t)rows;
   const dim3 grid((unsigned)((rows + RV_GQ_BATCH - 1) / RV_GQ_BATCH));
   hipLaunchKernelGGL(k_grasp_quality, grid, dim3(RV_GQ_TPB), lds, w->stream, a, d_weights);
+  HIPCHK(hipGetLastError());
+  return RV_OK;
+}
+int rv_grasp_refine(rv_world* w, const rv_grasp_refine_params* h_params, const rv_antipodal_params* h_sampler,
+                    const float* d_depth, const float* d_grasps, const float* d_scores, const int32_t* d_count,
+                    const int32_t* d_status, int32_t k, float* d_grasps_out, float* d_actions4_out,
+                    int32_t* d_parent, int32_t* d_count_out) {
+  WCHK(w);
+  if (!h_params || !h_sampler) return fail(RV_ERR_VALUE, "rv_grasp_refine: null params");
+  NEED(d_depth, "rv_grasp_refine"); NEED(d_grasps, "rv_grasp_refine"); NEED(d_scores, "rv_grasp_refine");
+  NEED(d_grasps_out, "rv_grasp_refine");
+  const rv_grasp_refine_params& p = *h_params;
+  if (!aligned_to(d_depth, 4) || !aligned_to(d_grasps, 4) || !aligned_to(d_scores, 4) || !aligned_to(d_count, 4) ||
+      !aligned_to(d_status, 4) || !aligned_to(d_grasps_out, 4) || !aligned_to(d_actions4_out, 4) || !aligned_to(d_parent, 4) ||
+      !aligned_to(d_count_out, 4))
+    return fail(RV_ERR_VALUE, "rv_grasp_refine: the buffers must be 4-byte aligned");
+  if (d_grasps_out == d_grasps) return fail(RV_ERR_VALUE, "rv_grasp_refine: d_grasps_out must not be d_grasps");
+  if (k < 1 || k > RV_AP_MAX_SAMPLES) return fail(RV_ERR_VALUE, "rv_grasp_refine: k outside [1, RV_AP_MAX_SAMPLES]");
+  if (p.n_elites < 1 || p.n_elites > k) return fail(RV_ERR_VALUE, "rv_grasp_refine: n_elites outside [1, k]");
+  if (p.height < 1 || p.width < 1) return fail(RV_ERR_VALUE, "rv_grasp_refine: height or width < 1");
+  const float big = 3.402823466e38f;
+  const auto sigma_ok = [big](float v) { return v >= 0.0f && v <= big; };
+  if (!sigma_ok(p.sigma_center) || !sigma_ok(p.sigma_angle) || !sigma_ok(p.sigma_depth))
+    return fail(RV_ERR_VALUE, "rv_grasp_refine: a sigma is negative or not finite");
+  if (p.macro_index < 0 || p.macro_index >= RV_GR_MAX_MACRO_INDEX) return fail(RV_ERR_VALUE, "rv_grasp_refine: macro_index outside [0, 2^24)");
+  if (p.iteration < 0 || p.iteration >= RV_GR_MAX_ITERATION) return fail(RV_ERR_VALUE, "rv_grasp_refine: iteration outside [0, 2^26)");
+  if (p.reserved[0] != 0 || p.reserved[1] != 0 || p.reserved[2] != 0) return fail(RV_ERR_VALUE, "rv_grasp_refine: a reserved word is not zero");
+  if (d_actions4_out && w->cfg.env_type != RV_ENV_GRASP) return fail(RV_ERR_VALUE, "rv_grasp_refine: d_actions4_out needs a Grasp4DofEnv world");
+  GrArgs a;
+  int rc = antipodal_geometry(*h_sampler, p.height, p.width, "rv_grasp_refine", &a.ap); if (rc != RV_OK) return rc;
+  a.ap.depth = d_depth;
+  a.p = p; a.grasps = d_grasps; a.scores = d_scores; a.count = d_count; a.status = d_status;
+  a.grasps_out = d_grasps_out; a.actions4 = d_actions4_out; a.parent = d_parent; a.count_out = d_count_out; a.K = k;
+  // one wave per env, four envs per workgroup
+  const int per = RV_GR_TPB / 64;
+  hipLaunchKernelGGL(k_grasp_refine, dim3((unsigned)((w->n + per - 1) / per)), dim3(RV_GR_TPB), 0, w->stream, w->d_envs, w->n, w->d_cfg, a);
   HIPCHK(hipGetLastError());
   return RV_OK;
 }

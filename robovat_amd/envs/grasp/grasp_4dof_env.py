@@ -44,6 +44,7 @@ class VecGrasp4DofEnv(object):
         self._macro_index = 0
         self.antipodal_status = self.antipodal_image_grasps = None
         self.antipodal_count = self.antipodal_actions4 = None
+        self.refine_parent = None
         self._plan_worlds = {}
 
     device = property(lambda s: s.world.device)
@@ -146,6 +147,36 @@ class VecGrasp4DofEnv(object):
         crop = dict(crop, crop_height=model.sizes['height'], crop_width=model.sizes['width'])
         images, grasp_depths = self.grasp_images(image_grasps, depth, **crop)
         return self.world.grasp_quality(images, grasp_depths, model)
+
+    def refine_grasps(self, scores, num_elites, sigmas, iteration, image_grasps=None, depth=None, config=None, seed=0):
+        """One cross-entropy step on the candidates (rv_grasp_refine), one launch: the K rows of
+        ``antipodal_image_grasps`` are ranked per env by ``scores`` [N, K] (logits of ``grasp_qualities``, rewards of
+        ``try_grasps``, ...), the best ``num_elites`` stay -- in rank order, bit for bit, so row 0 is the best candidate --
+        and every other row becomes a child of an elite: centre, axis angle and depth perturbed by normals of ``sigmas`` =
+        (pixels, radians, metres), kept when it passes the sampler's boundary and depth-window checks of ``config`` (an
+        AntipodalGrasp4DofPolicy config; None: the default), else its parent again.  ``iteration``: the refinement round,
+        part of the Philox key with the env's next step index and ``seed``.  ``depth`` [N, H, W] (None: rendered now,
+        without sensor noise).  ``image_grasps`` None: the last sampling or refinement call's rows with their
+        ``antipodal_count`` / ``antipodal_status`` (ValueError if there was none); given: [N, K, 5], every row a candidate.
+        Replaces ``antipodal_image_grasps``, ``antipodal_actions4`` and ``antipodal_count`` (K, or 0 for an env without a
+        candidate, whose rows stay as they are); keeps ``refine_parent`` int32 [N, K]: the input row of each output row,
+        -1 - row for a child that fell back to its parent.  Returns the new candidates in the env's ACTION.TYPE."""
+        from robovat_amd import lib
+        count = status = None
+        if image_grasps is None:
+            image_grasps, count, status = self.antipodal_image_grasps, self.antipodal_count, self.antipodal_status
+            if image_grasps is None or image_grasps.dim() != 3:
+                raise ValueError('refine_grasps: no image grasps given and no sample_antipodal_candidates call before this one')
+        if depth is None:
+            depth, _ = self.world.render()
+        sc, sa, sd = [float(v) for v in sigmas]
+        params = lib.grasp_refine_params(n_elites=num_elites, sigma_center=sc, sigma_angle=sa, sigma_depth=sd,
+                                         macro_index=self._macro_index, iteration=iteration, seed=seed)
+        g, a, parent, cnt = self.world.grasp_refine(depth, image_grasps, scores, params, lib.antipodal_params(config),
+                                                    count=count, status=status, actions4=True)
+        self.antipodal_image_grasps, self.antipodal_actions4, self.antipodal_count = g, a, cnt
+        self.refine_parent = parent
+        return a if self.config.ACTION.TYPE == 'CUBOID' else g
 
     def collect_grasp_samples(self, num_samples, depth=None, config=None, **crop):
         """Labelled grasp samples of the envs as they are now: one depth image (``depth`` [N, H, W]; None: rendered once,
@@ -344,10 +375,23 @@ class Grasp4DofEnv(object):
         out = self._vec.collect_grasp_samples(num_samples, depth, config, **crop)
         return {key: v[0].cpu().numpy() for key, v in out.items()}
 
+    def refine_grasps(self, scores, num_elites, sigmas, iteration, image_grasps=None, depth=None, config=None, seed=0):
+        """``VecGrasp4DofEnv.refine_grasps`` for this env: ``scores`` [K], ``image_grasps`` [K, 5] (None: those of the last
+        sampling or refinement call), ``depth`` [H, W] (None: rendered now).  Returns NumPy [K, 4] or [K, 5] by ACTION.TYPE."""
+        if image_grasps is not None:
+            image_grasps = np.asarray(image_grasps, np.float32).reshape(1, -1, 5)
+        if depth is not None:
+            depth = np.asarray(depth, np.float32).reshape((1,) + np.shape(depth)[-2:])
+        if not hasattr(scores, 'dim'):
+            scores = np.asarray(scores, np.float32)
+        out = self._vec.refine_grasps(scores.reshape(1, -1), num_elites, sigmas, iteration, image_grasps, depth, config, seed)
+        return out[0].cpu().numpy()
+
     antipodal_status = property(lambda s: s._vec.antipodal_status)
     antipodal_count = property(lambda s: s._vec.antipodal_count)
     antipodal_image_grasps = property(lambda s: s._vec.antipodal_image_grasps)
     antipodal_actions4 = property(lambda s: s._vec.antipodal_actions4)
+    refine_parent = property(lambda s: s._vec.refine_parent)
 
     def save_state(self):
         return self._vec.save_state()

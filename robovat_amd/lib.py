@@ -41,6 +41,7 @@ SYMBOLS = [
     'rv_get_route_field', 'rv_policy_route_multi', 'rv_plan_propose_route',
     'rv_grasp_crops',
     'rv_grasp_quality_weight_count', 'rv_grasp_quality',
+    'rv_grasp_refine',
 ]
 
 _EXC = {abi.RV_ERR_VALUE: ValueError, abi.RV_ERR_STATE: RuntimeError,
@@ -185,7 +186,7 @@ def load():
         getattr(lib, name).argtypes = [vp, vp]
     abi.bind_state_api(lib)
     for api in (abi.ANTIPODAL_API, abi.CEM_API, abi.DEPTH_NOISE_API, abi.PUSH_PROPOSAL_API, abi.PUSH_ROUTE_API,
-                abi.GRASP_CROP_API, abi.GRASP_QUALITY_API):
+                abi.GRASP_CROP_API, abi.GRASP_QUALITY_API, abi.GRASP_REFINE_API):
         for name, (res, args) in api.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, list(args)
@@ -322,6 +323,24 @@ def grasp_crop_params(crop_height=32, crop_width=32, step=3, **overrides):
     for k, v in overrides.items():
         if k not in names:
             raise TypeError('grasp_crop_params: unknown field %r' % (k,))
+        setattr(p, k, type(getattr(p, k))(v))
+    return p
+
+
+def grasp_refine_params(n_elites=1, sigma_center=3.0, sigma_angle=0.15, sigma_depth=0.005, macro_index=0, iteration=0,
+                        seed=0, **overrides):
+    """An ``rv_grasp_refine_params``: ``n_elites`` kept rows, the standard deviations of a child's centre (pixels), axis
+    angle (radians) and depth (metres), and the Philox arguments ``macro_index`` (the env.step() being chosen),
+    ``iteration`` (the refinement round) and ``seed``.  The default sigmas are BUILD-CHOSEN and unmeasured.
+    ``height`` / ``width`` start at 0 -- ``World.grasp_refine`` fills them in from the tensor -- and keyword arguments
+    override fields by their C names."""
+    p = abi.rv_grasp_refine_params(height=0, width=0, macro_index=int(macro_index), iteration=int(iteration),
+                                   seed=int(seed) & 0xFFFFFFFF, n_elites=int(n_elites), sigma_center=float(sigma_center),
+                                   sigma_angle=float(sigma_angle), sigma_depth=float(sigma_depth))
+    names = [n for n, _ in abi.rv_grasp_refine_params._fields_ if n != 'reserved']
+    for k, v in overrides.items():
+        if k not in names:
+            raise TypeError('grasp_refine_params: unknown field %r' % (k,))
         setattr(p, k, type(getattr(p, k))(v))
     return p
 
@@ -759,6 +778,45 @@ class World(object):
         desc = model.descriptor()
         check(self.lib.rv_grasp_quality(self.h, C.byref(desc), self._ptr(blob), self._ptr(x), self._ptr(z), k, self._ptr(out)))
         return out
+
+    # -- cross-entropy refinement of grasp candidates (include/rovat.h: rv_grasp_refine)
+    def grasp_refine(self, depth, grasps, scores, params, sampler_params, count=None, status=None, actions4=False):
+        """rv_grasp_refine: the next generation of grasp candidates.  ``grasps`` [N, K, 5] are ranked per env by ``scores``
+        [N, K]; the first ``params.n_elites`` stay, in rank order, and every further row is a child of an elite -- its centre,
+        axis angle and depth perturbed by normals of ``params``' sigmas -- that passes the sampler's boundary and
+        depth-window checks of ``sampler_params`` (``antipodal_params(config)``) on ``depth`` [N, H, W], or else its parent
+        again.  ``count`` / ``status`` int32 [N]: the sampler's outputs (None: every row is a candidate).  ``params``:
+        ``grasp_refine_params(...)``; its height and width are taken from the tensor.  Returns (grasps [N, K, 5], 4-DoF
+        actions [N, K, 4] or None -- ``actions4=True`` needs a grasp world --, parent int32 [N, K]: the input row an output
+        row came from, -1 - row for a child that fell back, count int32 [N]: K, or 0 for an env without a candidate)."""
+        torch = self.torch
+        d = torch.as_tensor(depth, dtype=torch.float32, device=self.device)
+        if d.dim() != 3 or int(d.shape[0]) != self.n:
+            raise ValueError('grasp_refine: depth must be [N, H, W] with N = %d, got %s' % (self.n, tuple(d.shape)))
+        g = torch.as_tensor(grasps, dtype=torch.float32, device=self.device)
+        if g.dim() != 3 or int(g.shape[0]) != self.n or int(g.shape[2]) != 5:
+            raise ValueError('grasp_refine: grasps must be [N, K, 5] with N = %d, got %s' % (self.n, tuple(g.shape)))
+        k = int(g.shape[1])
+        s = torch.as_tensor(scores, dtype=torch.float32, device=self.device)
+        if tuple(s.shape) != (self.n, k):
+            raise ValueError('grasp_refine: scores must be [N, K] = [%d, %d], got %s' % (self.n, k, tuple(s.shape)))
+        d, g, s = d.contiguous(), g.contiguous(), s.contiguous()
+        cnt = st = None
+        if count is not None:
+            cnt = self._in(count, (self.n,), torch.int32)
+        if status is not None:
+            st = self._in(status, (self.n,), torch.int32)
+        p = abi.rv_grasp_refine_params.from_buffer_copy(params)
+        p.height, p.width = int(d.shape[1]), int(d.shape[2])
+        rows = min(max(k, 1), abi.RV_AP_MAX_SAMPLES)      # (the library refuses a K outside [1, RV_AP_MAX_SAMPLES])
+        out = self._new((self.n, rows, 5), torch.float32)
+        a = self._new((self.n, rows, 4), torch.float32) if actions4 else None
+        par = self._new((self.n, rows), torch.int32)
+        cout = self._new((self.n,), torch.int32)
+        opt = lambda t: None if t is None else self._ptr(t)
+        check(self.lib.rv_grasp_refine(self.h, C.byref(p), C.byref(sampler_params), self._ptr(d), self._ptr(g), self._ptr(s),
+                                       opt(cnt), opt(st), k, self._ptr(out), opt(a), self._ptr(par), self._ptr(cout)))
+        return out, a, par, cout
 
     # -- env states as data (include/rovat.h: rv_state_* / rv_branch / rv_plan_simulate)
     def state_bytes(self):

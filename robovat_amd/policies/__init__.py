@@ -151,6 +151,85 @@ class GraspQualityPolicy(Policy):
         return actions
 
 
+class CEMGraspPolicy(Policy):
+    """``GraspQualityPolicy`` with a search around the good candidates: one render, ``num_samples`` (K)
+    antipodal candidates (``sample_antipodal_candidates``), then ``num_iterations`` times { score; ``refine_grasps``: keep
+    the ``num_elites`` best, resample the rest around them } with the sigmas times ``decay ** t`` in round t, and a final
+    scoring.  A last ``refine_grasps`` call with ``num_elites = K`` and zero sigmas sorts the rows, and the action is row 0
+    -- the ranking is rv_grasp_refine's (descending, the lower index among equals, NaNs last), no ranking code sits here.
+    ``score='model'``: the logits of ``model`` (``grasp_qualities``), nothing is executed; ``score='simulator'``: the
+    rewards of ``try_grasps(antipodal_actions4)``, every candidate executed on a copy of its env, no model needed -- how
+    far refinement goes with a perfect ranking.  Elites are kept bit for bit, so an env's best score never goes down from
+    one scoring to the next.  Where an env has no candidate, or its best score is NaN (every candidate's is), the action
+    is candidate 0 of the first sampling, the grasp AntipodalGrasp4DofPolicy takes.  ``num_iterations = 0`` with
+    ``score='model'`` is ``GraspQualityPolicy``'s action (which, unlike this one, also falls back to candidate 0 when only
+    SOME logit is NaN).  The action is in the env's ACTION.TYPE.  ``num_elites`` None: max(1, K // 4).  The default sigmas
+    (3 px, 0.15 rad, 5 mm) and ``decay`` are BUILD-CHOSEN: nobody has measured them.  Kept: ``last_scores``, a list with
+    one [N, K] tensor per scoring; ``last_grasps`` [N, K, 5], the sorted final rows; ``last_choice_parentage``, the
+    ``refine_parent`` [N, K] of every ``refine_grasps`` call in order (the sort's last), through which row 0 traces back
+    to a candidate of the first sampling.  ``crop``: ``step`` of the crops.  ``env``: a ``VecGrasp4DofEnv`` or a
+    ``Grasp4DofEnv``."""
+
+    def __init__(self, env, num_samples, num_iterations=2, num_elites=None, model=None, score='model', sigma_center=3.0,
+                 sigma_angle=0.15, sigma_depth=0.005, decay=0.5, seed=0, config=None, **crop):
+        config = config or configs.AttrDict(configs.ANTIPODAL_GRASP_4DOF_POLICY_CONFIG)
+        super(CEMGraspPolicy, self).__init__(env, config)
+        self._vec = getattr(env, '_vec', env)      # (a Grasp4DofEnv is a VecGrasp4DofEnv of one)
+        self._single = self._vec is not env
+        if not hasattr(self._vec, 'refine_grasps'):
+            raise NotImplementedError('CEMGraspPolicy needs a Grasp4DofEnv / VecGrasp4DofEnv')
+        self.num_samples, self.num_iterations = int(num_samples), int(num_iterations)
+        if self.num_samples < 1 or self.num_iterations < 0:
+            raise ValueError('CEMGraspPolicy: num_samples must be positive and num_iterations not negative')
+        self.num_elites = max(1, self.num_samples // 4) if num_elites is None else int(num_elites)
+        if not 1 <= self.num_elites <= self.num_samples:
+            raise ValueError('CEMGraspPolicy: num_elites must be in [1, num_samples]')
+        if score not in ('model', 'simulator'):
+            raise ValueError("CEMGraspPolicy: score must be 'model' or 'simulator'")
+        if score == 'model' and model is None:
+            raise ValueError("CEMGraspPolicy: score='model' needs a model")
+        self.model, self.score, self.crop = model, score, dict(crop)
+        self.sigmas = (float(sigma_center), float(sigma_angle), float(sigma_depth))
+        self.decay, self.seed = float(decay), int(seed)
+        self.last_scores = self.last_grasps = self.last_choice_parentage = None
+
+    def _scores(self, depth):
+        v = self._vec
+        if self.score == 'model':
+            return v.grasp_qualities(self.model, v.antipodal_image_grasps, depth, **self.crop)
+        return v.try_grasps(v.antipodal_actions4)[0]
+
+    def _action(self, observation):
+        v = self._vec
+        t = v.world.torch
+        depth = None if observation is None else observation.get('depth')
+        if depth is not None and self._single:
+            depth = np.asarray(depth, np.float32).reshape((1,) + np.shape(depth)[-2:])
+        if depth is None:
+            depth, _ = v.world.render()      # (one render serves the sampler, the crops and the refinement)
+        first = v.sample_antipodal_candidates(self.num_samples, depth, self.config)
+        if self._single and int(v.antipodal_status[0].item()) != 1:
+            raise ValueError('Failed to sample any valid grasp (antipodal status %d).' % int(v.antipodal_status[0].item()))
+        first0 = first[:, 0].clone()
+        scores, parents = [], []
+        for it in range(self.num_iterations):
+            scores.append(self._scores(depth))
+            v.refine_grasps(scores[-1], self.num_elites, [s * self.decay ** it for s in self.sigmas], it, depth=depth,
+                            config=self.config, seed=self.seed)
+            parents.append(v.refine_parent)
+        scores.append(self._scores(depth))
+        cand = v.refine_grasps(scores[-1], self.num_samples, (0.0, 0.0, 0.0), self.num_iterations, depth=depth,
+                               config=self.config, seed=self.seed)
+        parents.append(v.refine_parent)
+        best = scores[-1].gather(1, v.refine_parent[:, :1].long().clamp(min=0))[:, 0]
+        fallback = (v.antipodal_count == 0) | t.isnan(best)
+        actions = t.where(fallback[:, None], first0, cand[:, 0])
+        self.last_scores, self.last_grasps, self.last_choice_parentage = scores, v.antipodal_image_grasps, parents
+        if self._single:
+            return actions[0].cpu().numpy()
+        return actions
+
+
 class ShootingPushPolicy(Policy):
     """Random-shooting model-predictive control with the simulator as the model: per env ``num_samples`` candidate
     action sequences of ``horizon`` steps, drawn U(-1, 1) from a torch generator seeded with ``seed``, are tried on

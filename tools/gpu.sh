@@ -32,6 +32,8 @@
 #   grasp_quality  tools/grasp_quality_bench.py: rv_grasp_quality against torch's eager forward and the f32 matrix peak, and
 #                  the success rate of GraspQualityPolicy next to candidate 0 and the look-ahead; then the kernel's own
 #                  duration from a profiler run of the kernel half, and its resources
+#   grasp_refine   tools/grasp_refine_bench.py: rv_grasp_refine against a torch restatement of the step and next to one
+#                  scoring, and the success rate of CEMGraspPolicy next to the other grasp policies; the kernel's resources
 #   lanes          SQ_THREAD_CYCLES_VALU / SQ_ACTIVE_INST_VALU lane-utilisation pass (headline and no-deactivation)
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}; TAG=$1; shift
 O=$R/gpurun_out/$TAG; mkdir -p $O; cd $R
@@ -107,6 +109,12 @@ for STAGE in "$@"; do
       python tools/kernel_resources.py > $O/kernel_resources_all.txt 2>&1
       grep -h "^kernel\|grasp_quality" $O/kernel_resources_all.txt > $O/grasp_quality_kernel_resources.txt
       tail -30 $O/grasp_quality_bench.txt; cat $O/grasp_quality_kernel_stats.txt ;;
+    grasp_refine)
+      timeout -k 10 1100 python tools/grasp_refine_bench.py --out $O/grasp_refine_bench.txt > $O/grasp_refine_bench.log 2>&1
+      echo "grasp_refine rc=$?" >> $O/time.txt
+      python tools/kernel_resources.py > $O/kernel_resources_all.txt 2>&1
+      grep -h "^kernel\|grasp_refine" $O/kernel_resources_all.txt > $O/grasp_refine_kernel_resources.txt
+      tail -30 $O/grasp_refine_bench.txt; cat $O/grasp_refine_kernel_resources.txt ;;
     lanes)
       cd /tmp
       for V in head nd; do
