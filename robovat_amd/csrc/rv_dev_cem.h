@@ -30,8 +30,8 @@
 //   c1 = the policy's seed (rv_cem_params.seed)
 //   c2 = global env id (env_id_offset + n)
 //   c3 = (RV_STREAM_CEM << 24) | plan_index      plan_index in [0, 2^24)
-// -- a function of nothing else: not of N, S, H or of the other envs of the world.  c3 cannot meet another stream's: those
-// are the bare ids 1 .. 7 or (5 << 24) | index (rv_dev_grasp_sampler.h).  Arguments outside the ranges are refused.
+// -- a function of nothing else: not of N, S, H or of the other envs of the world.  c3 cannot meet another stream's: the ids
+// are distinct (the table of RV_STREAM_* in rv_dev_math.h).  Arguments outside the ranges are refused.
 //
 // k_cem_sample: one lane per (n, j, q); x[n][j][d] = fclampr(mean[n][d] + std[n][d] * z[d], -1, 1) (the product rounded,
 // then the sum); with keep_mean, candidate 0 is fclampr(mean[n][d], -1, 1) and draws nothing.  x is [N][S][H][G][4], the
@@ -59,7 +59,6 @@
 
 namespace rv {
 
-#define RV_STREAM_CEM 8u
 #define RV_CEM_MAX_TPB 1024
 #define RV_CEM_MAX_ITERATION (1 << 15)
 #define RV_CEM_MAX_PLAN_INDEX (1 << 24)

@@ -14,7 +14,7 @@
 //   c2 = global env id (env_id_offset + n)
 //   c3 = (RV_STREAM_DEPTH_NOISE << 24) | draw_index      draw_index in [0, 2^24)
 // -- a function of nothing else: not of N, not of the image size beyond the grid index, not of the other envs.  c3 cannot
-// meet another stream's: those are the bare ids 1 .. 7, (5 << 24) | index and (8 << 24) | index.  q < 2^31: a grid block
+// meet another stream's: the ids are distinct (the table of RV_STREAM_* in rv_dev_math.h).  q < 2^31: a grid block
 // never meets a scalar block.
 //
 // Per-image scalars (dn_scalars), from the scalar blocks:
@@ -67,7 +67,6 @@
 
 namespace rv {
 
-#define RV_STREAM_DEPTH_NOISE 9u
 #define RV_DN_MAX_DRAW_INDEX (1 << 24)
 #define RV_DN_MAX_RESCALE 8
 #define RV_DN_SCALAR_BLOCK 0x80000000u

@@ -1,5 +1,5 @@
 // rv_dev_env_types.h -- the state layout of one env and the constants every layer of the env program shares:
-// the profiling hooks (RV_STOP*, RV_PROF*, RV_PCNT), the random stream ids, the manifold slot indices (RV_TIDX,
+// the profiling hooks (RV_STOP*, RV_PROF*, RV_PCNT), the manifold slot indices (RV_TIDX,
 // RV_BBIDX, RV_AIDX), JTarget / LTarget (controllable_body.py:28-233), DevEnv (the persistent block in HBM, staged in
 // LDS), Row, Scratch, Shared, Consts, and the small predicates on them (brk_*, body_on, body_movable, ...).
 #pragma once
@@ -38,10 +38,6 @@ __device__ __forceinline__ void g_shared_cnt(int i, int n);
 #define RV_PCNT(i, n)
 #endif
 
-#define RV_STREAM_RESET  1u
-#define RV_STREAM_RANDOM 2u
-#define RV_STREAM_HEUR   3u
-#define RV_STREAM_CAMERA 4u
 #define RV_STEPS_TO_CHECK_DONE 100   // controllable_body.py:21
 #define RV_STEPS_TO_UPDATE_IK  10    // controllable_body.py:24
 

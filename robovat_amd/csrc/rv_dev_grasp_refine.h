@@ -50,8 +50,8 @@
 //   c2 = global env id (env_id_offset + n)
 //   c3 = (RV_STREAM_GRASP_REFINE << 24) | macro_index      macro_index in [0, 2^24)
 // -- a function of nothing else: not of N, K, n_elites or the other envs.  The components 0 .. 3 are the block's four
-// output words.  c3 cannot meet another stream's: those are the bare ids 1 .. 7 or (id << 24) | index with id 5 (the
-// sampler), 6, 8, 9, 10.  Arguments outside the ranges are refused.
+// output words.  c3 cannot meet another stream's: the ids are distinct (the table of RV_STREAM_* in
+// rv_dev_math.h).  Arguments outside the ranges are refused.
 //
 // Buffers and contract (rv_grasp_refine in rv_kernels.hip).  d_depth [N][H][W]; d_grasps [N][K][5] as
 // rv_policy_antipodal_multi or an earlier call wrote them; d_scores [N][K]; d_count, d_status [N] or NULL; d_grasps_out
@@ -79,7 +79,6 @@
 #include "rv_dev_grasp_sampler.h"
 #include "rv_dev_cem.h"
 
-#define RV_STREAM_GRASP_REFINE 11u
 #define RV_GR_MAX_ITERATION (1 << 26)
 #define RV_GR_MAX_MACRO_INDEX (1 << 24)
 #define RV_GR_TPB 256

@@ -114,7 +114,6 @@
 
 namespace rv {
 
-#define RV_STREAM_GRASP 5u
 #define RV_AP_TPB 256
 #define RV_AP_WAVES (RV_AP_TPB / 64)
 #define RV_AP_DRAW_CTR 0xffffffffu   // counter word 0 of the depth draw: pair keys use pixel indices < 2^31

@@ -233,6 +233,21 @@ RV_DEV void quat_to_euler(q4 q, float* e) {
 }
 
 // ---- Philox4x32-10 ----
+// THE table of stream ids: every RV_STREAM_* of the project is defined here and nowhere else (tests/test_stream_ids.py).
+// A stream owns the counter word c3, either as the bare id or as (id << 24) | index with index < 2^24.  The ids are
+// pairwise distinct and 1 <= id < 256, so a bare id (< 2^24) never meets an (id << 24) | index word, and two of those
+// differ in their top byte: the key spaces are disjoint, which is what makes every draw "a function of nothing else".
+#define RV_STREAM_RESET          1u   // rv_dev_env.h, the reset of an env (rng_init, arg = reset_count): c3 = bare id
+#define RV_STREAM_RANDOM         2u   // rv_dev_env.h, the random policy (rng_init, arg = macro_index): c3 = bare id
+#define RV_STREAM_HEUR           3u   // k_policy_heuristic and the spread proposals' attempt stream (rv_dev_push_sampler.h; rng_init): c3 = bare id
+#define RV_STREAM_CAMERA         4u   // rv_dev_env.h, the camera's reset noise (rng_init, arg = reset_count): c3 = bare id
+#define RV_STREAM_GRASP          5u   // rv_dev_grasp_sampler.h, the antipodal samplers: c3 = (id << 24) | macro_index
+#define RV_STREAM_PUSH_PROPOSAL  6u   // rv_dev_push_sampler.h, the spread proposals: c3 = (id << 24) | plan_index
+#define RV_STREAM_PC             7u   // rv_dev_obs.h, the point-cloud sampler (c1 = ObsSnap.rng_arg): c3 = bare id
+#define RV_STREAM_CEM            8u   // rv_dev_cem.h, k_cem_sample: c3 = (id << 24) | plan_index
+#define RV_STREAM_DEPTH_NOISE    9u   // rv_dev_depth_noise.h, k_depth_noise_draw: c3 = (id << 24) | draw_index
+#define RV_STREAM_PUSH_ROUTE    10u   // rv_dev_push_route.h, the route proposals: c3 = (id << 24) | plan_index
+#define RV_STREAM_GRASP_REFINE  11u   // rv_dev_grasp_refine.h, k_grasp_refine: c3 = (id << 24) | macro_index
 struct Rng { uint32_t key0, key1; uint32_t c0, c1, c2, c3; uint32_t b0, b1, b2, b3; int idx; };
 RV_DEV void philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
                    uint32_t* o0, uint32_t* o1, uint32_t* o2, uint32_t* o3) {

@@ -25,8 +25,6 @@
 
 namespace rv {
 
-#define RV_STREAM_PC 7u
-
 // what the camera needs to know about one env at observation time
 struct ObsSnap {
   float pose[RV_MAXB][7];   // pos3, quat4 (xyzw)

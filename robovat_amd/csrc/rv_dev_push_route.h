@@ -46,7 +46,7 @@
 //     c0 = (step << 26) | (kg << 16) | a        step < 64, kg < 1024, a < 2^15
 //     c1 = the policy's seed (rv_push_route_params.seed)
 //     c2 = gid
-//     c3 = (RV_STREAM_PUSH_ROUTE << 24) | plan_index      plan_index in [0, 2^24); stream ids 1 .. 9 are taken
+//     c3 = (RV_STREAM_PUSH_ROUTE << 24) | plan_index      plan_index in [0, 2^24); the ids: rv_dev_math.h
 // The first good attempt wins (RV_HP_FOUND); with none in max_attempts, attempt max_attempts - 1 as drawn
 // (RV_HP_EXHAUSTED).  With keep_nominal, candidate kg == 0 draws nothing: its one attempt is (0, 0.5 * (back_lo +
 // back_hi), 0, 1), FOUND or EXHAUSTED by the same test.  An env whose body 0 is not movable gets the action (0, 0, 0, 0)
@@ -64,7 +64,6 @@
 
 namespace rv {
 
-#define RV_STREAM_PUSH_ROUTE 10u
 #define RV_PR_GRID 8
 #define RV_PR_CELLS (RV_PR_GRID * RV_PR_GRID)
 #define RV_PR_NONE 255

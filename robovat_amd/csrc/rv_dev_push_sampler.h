@@ -46,8 +46,8 @@
 //     c1 = the policy's seed (rv_push_proposal_params.seed)
 //     c2 = gid
 //     c3 = (RV_STREAM_PUSH_PROPOSAL << 24) | plan_index      plan_index in [0, 2^24)
-//   -- a function of nothing else: not of N, s, copies or of the other envs.  c3 cannot meet another stream's: those are
-//   the bare ids 1 .. 4 and 7, (5 << 24) | index, (8 << 24) | index and (9 << 24) | index; id 6 is used nowhere else.
+//   -- a function of nothing else: not of N, s, copies or of the other envs.  c3 cannot meet another stream's: the ids are
+//   distinct (the table of RV_STREAM_* in rv_dev_math.h).
 //   Hence s candidates of a source world (copies = 1) and one candidate of each of its s branches (s = 1, copies = s)
 //   are the same bits as long as the observations are: what lets step t of a candidate plan be drawn from that branch's
 //   own simulated state (rv_plan_propose, step = t).
@@ -73,7 +73,6 @@
 
 namespace rv {
 
-#define RV_STREAM_PUSH_PROPOSAL 6u
 #define RV_HP_WAVES 4
 #define RV_HP_MAX_STEP 64
 #define RV_HP_MAX_PLAN_INDEX (1 << 24)

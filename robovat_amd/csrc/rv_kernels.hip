@@ -1468,44 +1468,59 @@ int rv_branch(rv_world* dst, rv_world* src, int32_t s) {
   int rc = branch_check(dst, src, s, "rv_branch"); if (rc != RV_OK) return rc;
   return branch_copy(dst, src, s);
 }
+// the tail of rv_plan_simulate, rv_plan_propose and rv_plan_propose_route, after the caller's own checks: the launch
+// limit, the branch copy, then h x (before(t) -- what fills slice t of d_actions, if anything --, the slice into the envs,
+// one env.step(), the optional record)
+struct plan_no_before { int operator()(int) const { return RV_OK; } };
+extern "C++" template <class Before = plan_no_before>
+static int plan_steps(rv_world* w, rv_world* src, int s, int h, const float* d_actions, float* d_states, float* d_rewards,
+                      uint8_t* d_dones, const std::string& me, Before before = Before()) {
+  const int G = w->cfg.num_goal_steps > 0 ? w->cfg.num_goal_steps : 1;
+  if ((long long)w->n * G * 4 > 0x7fffffffLL || (long long)w->n * RV_MAXB > 0x7fffffffLL) return fail(RV_ERR_VALUE, me + ": too many envs for one launch");
+  int rc = branch_copy(w, src, s); if (rc != RV_OK) return rc;
+  for (int t = 0; t < h; ++t) {
+    rc = before(t); if (rc != RV_OK) return rc;
+    hipLaunchKernelGGL(k_plan_actions, dim3((unsigned)((w->n * G * 4 + 255) / 256)), dim3(256), 0, w->stream, w->d_envs, w->n, d_actions, G, h, t);
+    HIPCHK(hipGetLastError());
+    rc = launch_env<MODE_MACRO>(w, nullptr, 0, 0, 0, 0, 0, 0); if (rc != RV_OK) return rc;
+    if (d_states || d_rewards || d_dones) {
+      hipLaunchKernelGGL(k_plan_record, dim3((unsigned)((w->n * RV_MAXB + 255) / 256)), dim3(256), 0, w->stream, w->d_envs, w->n, h, t, d_states, d_rewards, d_dones);
+      HIPCHK(hipGetLastError());
+    }
+  }
+  return RV_OK;
+}
 int rv_plan_simulate(rv_world* plan, rv_world* src, const float* d_actions, int32_t s, int32_t h,
                      float* d_states, float* d_rewards, uint8_t* d_dones) {
   WCHK(src); WCHK(plan);
-  rv_world* w = plan;
   if (src->cfg.env_type == RV_ENV_GRASP || plan->cfg.env_type == RV_ENV_GRASP) return fail(RV_ERR_VALUE, "rv_plan_simulate: PushEnv worlds only");
   int rc = branch_check(plan, src, s, "rv_plan_simulate"); if (rc != RV_OK) return rc;
   if (h < 1) return fail(RV_ERR_VALUE, "rv_plan_simulate: h must be positive");
   NEED(d_actions, "rv_plan_simulate");
   if (!aligned_to(d_actions, 4) || !aligned_to(d_states, 8) || !aligned_to(d_rewards, 4)) return fail(RV_ERR_VALUE, "rv_plan_simulate: the states must be 8-byte aligned, actions and rewards 4-byte aligned");
-  const int G = w->cfg.num_goal_steps > 0 ? w->cfg.num_goal_steps : 1;
-  if ((long long)w->n * G * 4 > 0x7fffffffLL || (long long)w->n * RV_MAXB > 0x7fffffffLL) return fail(RV_ERR_VALUE, "rv_plan_simulate: too many envs for one launch");
-  rc = branch_copy(plan, src, s); if (rc != RV_OK) return rc;
-  for (int t = 0; t < h; ++t) {
-    hipLaunchKernelGGL(k_plan_actions, dim3((unsigned)((w->n * G * 4 + 255) / 256)), dim3(256), 0, w->stream, w->d_envs, w->n, d_actions, G, (int)h, t);
-    HIPCHK(hipGetLastError());
-    rc = launch_env<MODE_MACRO>(w, nullptr, 0, 0, 0, 0, 0, 0); if (rc != RV_OK) return rc;
-    if (d_states || d_rewards || d_dones) {
-      hipLaunchKernelGGL(k_plan_record, dim3((unsigned)((w->n * RV_MAXB + 255) / 256)), dim3(256), 0, w->stream, w->d_envs, w->n, (int)h, t, d_states, d_rewards, d_dones);
-      HIPCHK(hipGetLastError());
-    }
-  }
+  return plan_steps(plan, src, s, h, d_actions, d_states, d_rewards, d_dones, "rv_plan_simulate");
+}
+// the range checks hp_check and pr_check share: s, copies, env_id_offset % copies, max_attempts, plan_index, step, the
+// launch limit
+static int proposal_range_check(const rv_world* w, int32_t s, int32_t copies, int32_t max_attempts, int32_t plan_index, int32_t step, const std::string& me) {
+  if (s < 1 || s > RV_HP_MAX_SAMPLES) return fail(RV_ERR_VALUE, me + ": s outside [1, RV_HP_MAX_SAMPLES]");
+  if (copies < 1 || (long long)copies * s > RV_HP_MAX_SAMPLES) return fail(RV_ERR_VALUE, me + ": copies < 1 or copies * s > RV_HP_MAX_SAMPLES");
+  if (w->cfg.env_id_offset % copies != 0) return fail(RV_ERR_VALUE, me + ": env_id_offset is not a multiple of copies");
+  if (max_attempts < 1 || max_attempts > RV_HP_MAX_ATTEMPTS) return fail(RV_ERR_VALUE, me + ": max_attempts outside [1, RV_HP_MAX_ATTEMPTS]");
+  if (plan_index < 0 || plan_index >= RV_HP_MAX_PLAN_INDEX) return fail(RV_ERR_VALUE, me + ": plan_index outside [0, 2^24)");
+  if (step < 0 || step >= RV_HP_MAX_STEP) return fail(RV_ERR_VALUE, me + ": step outside [0, 64)");
+  if ((long long)w->n * s > 0x7fffffffLL) return fail(RV_ERR_VALUE, me + ": too many candidates for one launch");
   return RV_OK;
 }
 // the checks rv_policy_heuristic_multi and rv_plan_propose share: `w` is the world the kernel reads, p the params it is
 // launched with (rv_plan_propose: copies already x s, step the last one), s the candidates per env of w
 static int hp_check(const rv_world* w, const rv_push_proposal_params& p, int32_t s, const std::string& me) {
   if (w->cfg.env_type == RV_ENV_GRASP) return fail(RV_ERR_VALUE, me + ": a PushEnv world only");
-  if (s < 1 || s > RV_HP_MAX_SAMPLES) return fail(RV_ERR_VALUE, me + ": s outside [1, RV_HP_MAX_SAMPLES]");
   if (p.mode != RV_HP_EPISODE && p.mode != RV_HP_SPREAD) return fail(RV_ERR_VALUE, me + ": unknown mode");
-  if (p.copies < 1 || (long long)p.copies * s > RV_HP_MAX_SAMPLES) return fail(RV_ERR_VALUE, me + ": copies < 1 or copies * s > RV_HP_MAX_SAMPLES");
-  if (w->cfg.env_id_offset % p.copies != 0) return fail(RV_ERR_VALUE, me + ": env_id_offset is not a multiple of copies");
-  if (p.max_attempts < 1 || p.max_attempts > RV_HP_MAX_ATTEMPTS) return fail(RV_ERR_VALUE, me + ": max_attempts outside [1, RV_HP_MAX_ATTEMPTS]");
-  if (p.plan_index < 0 || p.plan_index >= RV_HP_MAX_PLAN_INDEX) return fail(RV_ERR_VALUE, me + ": plan_index outside [0, 2^24)");
-  if (p.step < 0 || p.step >= RV_HP_MAX_STEP) return fail(RV_ERR_VALUE, me + ": step outside [0, 64)");
+  int rc = proposal_range_check(w, s, p.copies, p.max_attempts, p.plan_index, p.step, me); if (rc != RV_OK) return rc;
   if (p.mode == RV_HP_EPISODE && (p.plan_index != 0 || p.step != 0 || p.seed != 0u || p.copies != 1))
     return fail(RV_ERR_VALUE, me + ": RV_HP_EPISODE takes plan_index, step and seed 0 and copies 1");
   if (!(p.start_margin >= 0.0f) || !(p.motion_margin >= 0.0f)) return fail(RV_ERR_VALUE, me + ": a margin is negative or NaN");
-  if ((long long)w->n * s > 0x7fffffffLL) return fail(RV_ERR_VALUE, me + ": too many candidates for one launch");
   return RV_OK;
 }
 // rows of (env, candidate) are (m * s + k) * h + t (csrc/rv_dev_push_sampler.h)
@@ -1539,7 +1554,6 @@ static int plan_propose_run(rv_world* plan, rv_world* src, const Params* h_param
                             float* d_rewards, uint8_t* d_dones, int32_t* d_status, const char* who, ModeOk mode_ok, Check check, Propose propose) {
   WCHK(src); WCHK(plan);
   const std::string me(who);
-  rv_world* w = plan;
   if (src->cfg.env_type == RV_ENV_GRASP || plan->cfg.env_type == RV_ENV_GRASP) return fail(RV_ERR_VALUE, me + ": PushEnv worlds only");
   int rc = branch_check(plan, src, s, who); if (rc != RV_OK) return rc;
   if (h < 1) return fail(RV_ERR_VALUE, me + ": h must be positive");
@@ -1556,21 +1570,10 @@ static int plan_propose_run(rv_world* plan, rv_world* src, const Params* h_param
   if (!d_actions) return fail(RV_ERR_VALUE, me + ": null buffer");
   if (!aligned_to(d_actions, 4) || !aligned_to(d_states, 8) || !aligned_to(d_rewards, 4) || !aligned_to(d_status, 4))
     return fail(RV_ERR_VALUE, me + ": the states must be 8-byte aligned, actions, rewards and status 4-byte aligned");
-  const int G = w->cfg.num_goal_steps > 0 ? w->cfg.num_goal_steps : 1;
-  if ((long long)w->n * G * 4 > 0x7fffffffLL || (long long)w->n * RV_MAXB > 0x7fffffffLL) return fail(RV_ERR_VALUE, me + ": too many envs for one launch");
-  rc = branch_copy(plan, src, s); if (rc != RV_OK) return rc;
-  for (int t = 0; t < h; ++t) {
+  return plan_steps(plan, src, s, h, d_actions, d_states, d_rewards, d_dones, me, [&](int t) {
     p.step = h_params->step + t;
-    rc = propose(w, p, (int)h, t); if (rc != RV_OK) return rc;
-    hipLaunchKernelGGL(k_plan_actions, dim3((unsigned)((w->n * G * 4 + 255) / 256)), dim3(256), 0, w->stream, w->d_envs, w->n, d_actions, G, (int)h, t);
-    HIPCHK(hipGetLastError());
-    rc = launch_env<MODE_MACRO>(w, nullptr, 0, 0, 0, 0, 0, 0); if (rc != RV_OK) return rc;
-    if (d_states || d_rewards || d_dones) {
-      hipLaunchKernelGGL(k_plan_record, dim3((unsigned)((w->n * RV_MAXB + 255) / 256)), dim3(256), 0, w->stream, w->d_envs, w->n, (int)h, t, d_states, d_rewards, d_dones);
-      HIPCHK(hipGetLastError());
-    }
-  }
-  return RV_OK;
+    return propose(plan, p, (int)h, t);
+  });
 }
 int rv_plan_propose(rv_world* plan, rv_world* src, const rv_push_proposal_params* h_params, int32_t s, int32_t h,
                     float* d_actions, float* d_states, float* d_rewards, uint8_t* d_dones, int32_t* d_status) {
@@ -1614,16 +1617,10 @@ static int route_field(rv_world* w) {
 // the checks rv_policy_route_multi and rv_plan_propose_route share, as hp_check
 static int pr_check(const rv_world* w, const rv_push_route_params& p, int32_t s, const std::string& me) {
   int rc = route_cfg_check(w, me); if (rc != RV_OK) return rc;
-  if (s < 1 || s > RV_HP_MAX_SAMPLES) return fail(RV_ERR_VALUE, me + ": s outside [1, RV_HP_MAX_SAMPLES]");
-  if (p.copies < 1 || (long long)p.copies * s > RV_HP_MAX_SAMPLES) return fail(RV_ERR_VALUE, me + ": copies < 1 or copies * s > RV_HP_MAX_SAMPLES");
-  if (w->cfg.env_id_offset % p.copies != 0) return fail(RV_ERR_VALUE, me + ": env_id_offset is not a multiple of copies");
-  if (p.max_attempts < 1 || p.max_attempts > RV_HP_MAX_ATTEMPTS) return fail(RV_ERR_VALUE, me + ": max_attempts outside [1, RV_HP_MAX_ATTEMPTS]");
-  if (p.plan_index < 0 || p.plan_index >= RV_HP_MAX_PLAN_INDEX) return fail(RV_ERR_VALUE, me + ": plan_index outside [0, 2^24)");
-  if (p.step < 0 || p.step >= RV_HP_MAX_STEP) return fail(RV_ERR_VALUE, me + ": step outside [0, 64)");
+  rc = proposal_range_check(w, s, p.copies, p.max_attempts, p.plan_index, p.step, me); if (rc != RV_OK) return rc;
   if (!(p.start_margin >= 0.0f) || !(p.angle_jitter >= 0.0f) || !(p.lateral >= 0.0f)) return fail(RV_ERR_VALUE, me + ": start_margin, angle_jitter or lateral is negative or NaN");
   if (!(p.back_lo <= p.back_hi)) return fail(RV_ERR_VALUE, me + ": back_lo > back_hi (or a NaN)");
   if (!(p.length_lo <= p.length_hi) || !(p.length_lo >= 0.0f)) return fail(RV_ERR_VALUE, me + ": length_lo > length_hi or length_lo < 0 (or a NaN)");
-  if ((long long)w->n * s > 0x7fffffffLL) return fail(RV_ERR_VALUE, me + ": too many candidates for one launch");
   return RV_OK;
 }
 static int pr_launch(rv_world* w, const rv_push_route_params& p, int s, int h, int t, float* d_actions, int32_t* d_status) {

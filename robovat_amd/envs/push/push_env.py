@@ -217,6 +217,17 @@ class VecPushEnv(object):
                                         seed=int(seed) & 0xFFFFFFFF, max_attempts=int(max_attempts),
                                         start_margin=float(start_margin), motion_margin=float(motion_margin))
 
+    def _candidates_out(self, out):
+        """(actions [M, s, G, 4], status) of ``lib.World.policy_*_multi`` -> (actions [N, S] + action shape, found bool)"""
+        a, st = out
+        return a.reshape((self.num_envs, int(a.shape[1])) + self.action_shape), st == abi.RV_HP_FOUND
+
+    def _plans_out(self, out):
+        """the five tensors of ``lib.World.plan_propose*`` -> (actions [N, S, H] + action shape, states, rewards, dones
+        bool, found bool)"""
+        a, st, r, d, status = out
+        return a.reshape(tuple(a.shape[:3]) + self.action_shape), st, r, d.bool(), status == abi.RV_HP_FOUND
+
     def sample_heuristic_candidates(self, num_samples, mode='spread', step=0, seed=0, max_attempts=20000,
                                     start_margin=0.05, motion_margin=0.01):
         """``num_samples`` aimed pushes per env from the last observation (``lib.World.policy_heuristic_multi``): each starts
@@ -227,8 +238,7 @@ class VecPushEnv(object):
         push.  Returns (actions float32 [N, S] + action shape, found bool [N, S]: False where ``max_attempts`` ran out
         and the last attempt is returned as drawn)."""
         p = self._proposal_params(mode, step, seed, max_attempts, start_margin, motion_margin)
-        a, st = self.world.policy_heuristic_multi(p, int(num_samples))
-        return a.reshape((self.num_envs, int(a.shape[1])) + self.action_shape), st == abi.RV_HP_FOUND
+        return self._candidates_out(self.world.policy_heuristic_multi(p, int(num_samples)))
 
     def propose_plans(self, num_samples, horizon, seed=0, max_attempts=20000, start_margin=0.05, motion_margin=0.01):
         """Look ahead with aimed pushes: ``num_samples`` plans of ``horizon`` steps per env, tried on copies of the env
@@ -239,8 +249,7 @@ class VecPushEnv(object):
         if int(num_samples) < 1:
             raise ValueError('propose_plans: num_samples must be positive')
         p = self._proposal_params('spread', 0, seed, max_attempts, start_margin, motion_margin)
-        a, st, r, d, status = self._plan_world(int(num_samples)).plan_propose(self.world, p, int(num_samples), int(horizon))
-        return a.reshape(tuple(a.shape[:3]) + self.action_shape), st, r, d.bool(), status == abi.RV_HP_FOUND
+        return self._plans_out(self._plan_world(int(num_samples)).plan_propose(self.world, p, int(num_samples), int(horizon)))
 
     def _route_params(self, step, seed, route):
         """``route``: fields of ``lib.push_route_params`` (max_attempts, keep_nominal, start_margin, angle_jitter, back_lo,
@@ -259,8 +268,7 @@ class VecPushEnv(object):
         ``lib.push_route_params``.  Returns (actions float32 [N, S] + action shape, found bool [N, S]: False where no
         attempt started ``start_margin`` clear of every body)."""
         p = self._route_params(step, seed, route)
-        a, st = self.world.policy_route_multi(p, int(num_samples))
-        return a.reshape((self.num_envs, int(a.shape[1])) + self.action_shape), st == abi.RV_HP_FOUND
+        return self._candidates_out(self.world.policy_route_multi(p, int(num_samples)))
 
     def propose_route_plans(self, num_samples, horizon, seed=0, **route):
         """``propose_plans`` with the pushes of ``sample_route_candidates`` (``lib.World.plan_propose_route``): step t of a
@@ -269,8 +277,7 @@ class VecPushEnv(object):
         if int(num_samples) < 1:
             raise ValueError('propose_route_plans: num_samples must be positive')
         p = self._route_params(0, seed, route)
-        a, st, r, d, status = self._plan_world(int(num_samples)).plan_propose_route(self.world, p, int(num_samples), int(horizon))
-        return a.reshape(tuple(a.shape[:3]) + self.action_shape), st, r, d.bool(), status == abi.RV_HP_FOUND
+        return self._plans_out(self._plan_world(int(num_samples)).plan_propose_route(self.world, p, int(num_samples), int(horizon)))
 
     def rollout(self, n_steps, auto_reset=True, record=True):
         before =self.world.env_counters().cpu().numpy()[:, [2, 4]] if (auto_reset and self._physics is not None) else None

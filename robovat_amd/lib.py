@@ -236,30 +236,31 @@ def antipodal_params(config=None):
     return p
 
 
+def _override(p, who, overrides):
+    """``p`` with the fields named in ``overrides`` set, each value converted to the field's type; a name that is no field
+    of the struct, or its ``reserved`` words, is a TypeError"""
+    names = [n for n, _ in p._fields_ if n != 'reserved']
+    for k, v in overrides.items():
+        if k not in names:
+            raise TypeError('%s: unknown field %r' % (who, k))
+        setattr(p, k, type(getattr(p, k))(v))
+    return p
+
+
 def plan_params(**overrides):
     """The ``rv_plan_params`` of ``get_reward_fn(..., is_planning=True)`` with the reference's defaults
     (push_reward.py:272-281): n_bodies 4, low level, goal 100, termination -100, dense 1, time -1, both terms on;
     gamma 1 (``rv_plan_score`` sums the rewards).  Keyword arguments override fields."""
     p = abi.rv_plan_params(n_bodies=abi.RV_MAXB, is_high_level=0, use_dense_reward=1, use_time_penalty=1,
                            goal_reward=100.0, termination_reward=-100.0, dense_reward=1.0, time_reward=-1.0, gamma=1.0)
-    names = [n for n, _ in abi.rv_plan_params._fields_]
-    for k, v in overrides.items():
-        if k not in names:
-            raise TypeError('plan_params: unknown field %r' % (k,))
-        setattr(p, k, type(getattr(p, k))(v))
-    return p
+    return _override(p, 'plan_params', overrides)
 
 
 def cem_params(**overrides):
     """An ``rv_cem_params``: plan_index 0, iteration 0, seed 0, keep_mean on, one elite, alpha 0 (no smoothing),
     min_std 0.  Keyword arguments override fields."""
     p = abi.rv_cem_params(plan_index=0, iteration=0, seed=0, keep_mean=1, n_elites=1, alpha=0.0, min_std=0.0)
-    names = [n for n, _ in abi.rv_cem_params._fields_]
-    for k, v in overrides.items():
-        if k not in names:
-            raise TypeError('cem_params: unknown field %r' % (k,))
-        setattr(p, k, type(getattr(p, k))(v))
-    return p
+    return _override(p, 'cem_params', overrides)
 
 
 def push_proposal_params(mode='spread', **overrides):
@@ -269,12 +270,7 @@ def push_proposal_params(mode='spread', **overrides):
     modes = {'episode': abi.RV_HP_EPISODE, 'spread': abi.RV_HP_SPREAD}
     p = abi.rv_push_proposal_params(mode=modes.get(mode, mode), plan_index=0, step=0, copies=1, max_attempts=20000, seed=0,
                                     start_margin=0.05, motion_margin=0.01)
-    names = [n for n, _ in abi.rv_push_proposal_params._fields_]
-    for k, v in overrides.items():
-        if k not in names:
-            raise TypeError('push_proposal_params: unknown field %r' % (k,))
-        setattr(p, k, type(getattr(p, k))(v))
-    return p
+    return _override(p, 'push_proposal_params', overrides)
 
 
 def push_route_params(**overrides):
@@ -283,12 +279,7 @@ def push_route_params(**overrides):
     unmeasured defaults around the one push that was tried).  Keyword arguments override fields."""
     p = abi.rv_push_route_params(plan_index=0, step=0, copies=1, max_attempts=256, seed=0, keep_nominal=1, start_margin=0.05,
                                  angle_jitter=0.3, back_lo=0.08, back_hi=0.16, lateral=0.02, length_lo=0.8, length_hi=1.2)
-    names = [n for n, _ in abi.rv_push_route_params._fields_]
-    for k, v in overrides.items():
-        if k not in names:
-            raise TypeError('push_route_params: unknown field %r' % (k,))
-        setattr(p, k, type(getattr(p, k))(v))
-    return p
+    return _override(p, 'push_route_params', overrides)
 
 
 def depth_noise_params(config=None, **overrides):
@@ -305,12 +296,7 @@ def depth_noise_params(config=None, **overrides):
     p = abi.rv_depth_noise_params(height=0, width=0, draw_index=0, seed=int(cfg.get('SEED', 0)) & 0xFFFFFFFF,
                                   gamma_shape=float(cfg.get('GAMMA_SHAPE', 1000.0)), prob=float(cfg.get('PROB', 0.5)),
                                   rescale_factor=int(r) if float(r) == int(r) else -1, sigma=float(cfg.get('SIGMA', 0.005)))
-    names = [n for n, _ in abi.rv_depth_noise_params._fields_]
-    for k, v in overrides.items():
-        if k not in names:
-            raise TypeError('depth_noise_params: unknown field %r' % (k,))
-        setattr(p, k, type(getattr(p, k))(v))
-    return p
+    return _override(p, 'depth_noise_params', overrides)
 
 
 def grasp_crop_params(crop_height=32, crop_width=32, step=3, **overrides):
@@ -319,12 +305,7 @@ def grasp_crop_params(crop_height=32, crop_width=32, step=3, **overrides):
     ``crop`` take their sizes from the caller): a 96-pixel window sampled to 32 x 32.  ``height`` / ``width`` start at 0
     -- ``World.grasp_crops`` fills them in from the tensor -- and keyword arguments override fields by their C names."""
     p = abi.rv_grasp_crop_params(height=0, width=0, crop_height=int(crop_height), crop_width=int(crop_width), step=int(step))
-    names = [n for n, _ in abi.rv_grasp_crop_params._fields_ if n != 'reserved']
-    for k, v in overrides.items():
-        if k not in names:
-            raise TypeError('grasp_crop_params: unknown field %r' % (k,))
-        setattr(p, k, type(getattr(p, k))(v))
-    return p
+    return _override(p, 'grasp_crop_params', overrides)
 
 
 def grasp_refine_params(n_elites=1, sigma_center=3.0, sigma_angle=0.15, sigma_depth=0.005, macro_index=0, iteration=0,
@@ -337,12 +318,7 @@ def grasp_refine_params(n_elites=1, sigma_center=3.0, sigma_angle=0.15, sigma_de
     p = abi.rv_grasp_refine_params(height=0, width=0, macro_index=int(macro_index), iteration=int(iteration),
                                    seed=int(seed) & 0xFFFFFFFF, n_elites=int(n_elites), sigma_center=float(sigma_center),
                                    sigma_angle=float(sigma_angle), sigma_depth=float(sigma_depth))
-    names = [n for n, _ in abi.rv_grasp_refine_params._fields_ if n != 'reserved']
-    for k, v in overrides.items():
-        if k not in names:
-            raise TypeError('grasp_refine_params: unknown field %r' % (k,))
-        setattr(p, k, type(getattr(p, k))(v))
-    return p
+    return _override(p, 'grasp_refine_params', overrides)
 
 
 def check(status):
@@ -879,22 +855,18 @@ class World(object):
         return st, r, d
 
     # -- aimed pushes as proposals for look-ahead (include/rovat.h: rv_policy_heuristic_multi / rv_plan_propose)
-    def policy_heuristic_multi(self, params, s):
-        """rv_policy_heuristic_multi: ``s`` aimed pushes for every env of this world.  ``params``:
-        ``push_proposal_params(...)``.  Returns (actions float32 [M, s, G, 4], status int32 [M, s]: abi.RV_HP_FOUND /
-        abi.RV_HP_EXHAUSTED)."""
+    def _multi(self, fn, params, s):
+        """``fn`` = rv_policy_heuristic_multi or rv_policy_route_multi: (actions float32 [M, s, G, 4], status int32 [M, s])"""
         s = int(s)
         rows = min(max(s, 1), abi.RV_HP_MAX_SAMPLES)      # (the library refuses an s outside [1, RV_HP_MAX_SAMPLES])
         a = self._new((self.n, rows, self.G, 4), self.torch.float32)
         st = self._new((self.n, rows), self.torch.int32)
-        check(self.lib.rv_policy_heuristic_multi(self.h, C.byref(params), s, self._ptr(a), self._ptr(st)))
+        check(fn(self.h, C.byref(params), s, self._ptr(a), self._ptr(st)))
         return a, st
 
-    def plan_propose(self, src, params, s, h):
-        """rv_plan_propose with this world as the plan world: ``s`` plans of ``h`` aimed pushes per env of ``src``, each
-        push drawn from its branch's own simulated state; ``src`` is only read.  ``params``: ``push_proposal_params(...)``
-        in 'spread' mode.  Returns (actions float32 [N, s, h, G, 4], states float32 [N, s, h, RV_MAXB, 2], rewards float32
-        [N, s, h], dones uint8 [N, s, h] -- as ``plan_simulate`` -- and status int32 [N, s, h])."""
+    def _propose(self, fn, src, params, s, h):
+        """``fn`` = rv_plan_propose or rv_plan_propose_route, this world the plan world: (actions, states, rewards, dones,
+        status)"""
         s, h = int(s), int(h)
         n, rs, rh = src.n, max(s, 1), max(h, 1)      # (the library refuses s < 1 and h < 1)
         a = self._new((n, rs, rh, self.G, 4), self.torch.float32)
@@ -902,9 +874,21 @@ class World(object):
         r = self._new((n, rs, rh), self.torch.float32)
         d = self._new((n, rs, rh), self.torch.uint8)
         status = self._new((n, rs, rh), self.torch.int32)
-        check(self.lib.rv_plan_propose(self.h, src.h, C.byref(params), s, h, self._ptr(a), self._ptr(st), self._ptr(r),
-                                       self._ptr(d), self._ptr(status)))
+        check(fn(self.h, src.h, C.byref(params), s, h, self._ptr(a), self._ptr(st), self._ptr(r), self._ptr(d), self._ptr(status)))
         return a, st, r, d, status
+
+    def policy_heuristic_multi(self, params, s):
+        """rv_policy_heuristic_multi: ``s`` aimed pushes for every env of this world.  ``params``:
+        ``push_proposal_params(...)``.  Returns (actions float32 [M, s, G, 4], status int32 [M, s]: abi.RV_HP_FOUND /
+        abi.RV_HP_EXHAUSTED)."""
+        return self._multi(self.lib.rv_policy_heuristic_multi, params, s)
+
+    def plan_propose(self, src, params, s, h):
+        """rv_plan_propose with this world as the plan world: ``s`` plans of ``h`` aimed pushes per env of ``src``, each
+        push drawn from its branch's own simulated state; ``src`` is only read.  ``params``: ``push_proposal_params(...)``
+        in 'spread' mode.  Returns (actions float32 [N, s, h, G, 4], states float32 [N, s, h, RV_MAXB, 2], rewards float32
+        [N, s, h], dones uint8 [N, s, h] -- as ``plan_simulate`` -- and status int32 [N, s, h])."""
+        return self._propose(self.lib.rv_plan_propose, src, params, s, h)
 
     # -- route-following pushes as proposals (include/rovat.h: rv_get_route_field / rv_policy_route_multi / rv_plan_propose_route)
     def route_field(self):
@@ -918,27 +902,13 @@ class World(object):
         """rv_policy_route_multi: ``s`` pushes of body 0 along the layout for every env of this world.  ``params``:
         ``push_route_params(...)``.  Returns (actions float32 [M, s, G, 4], status int32 [M, s]: abi.RV_HP_FOUND /
         abi.RV_HP_EXHAUSTED)."""
-        s = int(s)
-        rows = min(max(s, 1), abi.RV_HP_MAX_SAMPLES)      # (the library refuses an s outside [1, RV_HP_MAX_SAMPLES])
-        a = self._new((self.n, rows, self.G, 4), self.torch.float32)
-        st = self._new((self.n, rows), self.torch.int32)
-        check(self.lib.rv_policy_route_multi(self.h, C.byref(params), s, self._ptr(a), self._ptr(st)))
-        return a, st
+        return self._multi(self.lib.rv_policy_route_multi, params, s)
 
     def plan_propose_route(self, src, params, s, h):
         """rv_plan_propose_route with this world as the plan world: ``plan_propose`` with the pushes of
         ``policy_route_multi``.  ``params``: ``push_route_params(...)``.  Returns (actions, states, rewards, dones, status)
         as ``plan_propose``."""
-        s, h = int(s), int(h)
-        n, rs, rh = src.n, max(s, 1), max(h, 1)      # (the library refuses s < 1 and h < 1)
-        a = self._new((n, rs, rh, self.G, 4), self.torch.float32)
-        st = self._new((n, rs, rh, abi.RV_MAXB, 2), self.torch.float32)
-        r = self._new((n, rs, rh), self.torch.float32)
-        d = self._new((n, rs, rh), self.torch.uint8)
-        status = self._new((n, rs, rh), self.torch.int32)
-        check(self.lib.rv_plan_propose_route(self.h, src.h, C.byref(params), s, h, self._ptr(a), self._ptr(st), self._ptr(r),
-                                             self._ptr(d), self._ptr(status)))
-        return a, st, r, d, status
+        return self._propose(self.lib.rv_plan_propose_route, src, params, s, h)
 
     # -- state
     def _get(self, fn, shape, dtype):

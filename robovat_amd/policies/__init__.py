@@ -57,7 +57,45 @@ class AntipodalGrasp4DofPolicy(Policy):
         raise NotImplementedError('AntipodalGrasp4DofPolicy needs a Grasp4DofEnv / VecGrasp4DofEnv')
 
 
-class LookaheadGrasp4DofPolicy(Policy):
+class _GraspCandidatePolicy(Policy):
+    """What the policies that choose among ``sample_antipodal_candidates`` share.  ``env``: a ``VecGrasp4DofEnv`` or a
+    ``Grasp4DofEnv``, refused unless it has the method ``needs``."""
+
+    def __init__(self, env, config, needs):
+        config = config or configs.AttrDict(configs.ANTIPODAL_GRASP_4DOF_POLICY_CONFIG)
+        super(_GraspCandidatePolicy, self).__init__(env, config)
+        self._vec = getattr(env, '_vec', env)      # (a Grasp4DofEnv is a VecGrasp4DofEnv of one)
+        self._single = self._vec is not env
+        if not hasattr(self._vec, needs):
+            raise NotImplementedError('%s needs a Grasp4DofEnv / VecGrasp4DofEnv' % type(self).__name__)
+
+    def _depth_of(self, observation, render):
+        """the observation's depth as [N, H, W]; without one, a render of the world if ``render``, else None"""
+        depth = None if observation is None else observation.get('depth')
+        if depth is not None and self._single:
+            depth = np.asarray(depth, np.float32).reshape((1,) + np.shape(depth)[-2:])
+        if depth is None and render:
+            depth, _ = self._vec.world.render()
+        return depth
+
+    def _sample(self, depth):
+        """``num_samples`` candidates per env; a single env without one is refused as the reference's sampler refuses"""
+        v = self._vec
+        cand = v.sample_antipodal_candidates(self.num_samples, depth, self.config)
+        if self._single and int(v.antipodal_status[0].item()) != 1:
+            raise ValueError('Failed to sample any valid grasp (antipodal status %d).' % int(v.antipodal_status[0].item()))
+        return cand
+
+    def _first_index(self, qualifies):
+        """[N] the lowest index k at which ``qualifies`` (bool [N, K]) holds, else 0"""
+        t = self._vec.world.torch
+        n, k = qualifies.shape
+        index = t.arange(k, device=qualifies.device)[None, :].expand(n, k)
+        first = t.where(qualifies, index, t.full_like(index, k)).min(dim=1).values
+        return t.where(first < k, first, t.zeros_like(first))
+
+
+class LookaheadGrasp4DofPolicy(_GraspCandidatePolicy):
     """AntipodalGrasp4DofPolicy with one step of look-ahead, the simulator as the model: ``num_samples`` distinct
     antipodal grasps per env (``sample_antipodal_candidates``, the reference sampler's ``sample(depth, camera, K)``) are
     each tried on a bit-exact copy of the env (``try_grasps``), and the action is the lowest-index candidate whose
@@ -67,12 +105,7 @@ class LookaheadGrasp4DofPolicy(Policy):
     Kept: ``last_choice`` [N] and ``last_rewards`` [N, K].  ``env``: a ``VecGrasp4DofEnv`` or a ``Grasp4DofEnv``."""
 
     def __init__(self, env, num_samples, config=None):
-        config = config or configs.AttrDict(configs.ANTIPODAL_GRASP_4DOF_POLICY_CONFIG)
-        super(LookaheadGrasp4DofPolicy, self).__init__(env, config)
-        self._vec = getattr(env, '_vec', env)      # (a Grasp4DofEnv is a VecGrasp4DofEnv of one)
-        self._single = self._vec is not env
-        if not hasattr(self._vec, 'try_grasps'):
-            raise NotImplementedError('LookaheadGrasp4DofPolicy needs a Grasp4DofEnv / VecGrasp4DofEnv')
+        super(LookaheadGrasp4DofPolicy, self).__init__(env, config, 'try_grasps')
         self.num_samples = int(num_samples)
         if self.num_samples < 1:
             raise ValueError('LookaheadGrasp4DofPolicy: num_samples must be positive')
@@ -81,17 +114,9 @@ class LookaheadGrasp4DofPolicy(Policy):
     def _action(self, observation):
         v = self._vec
         t = v.world.torch
-        depth = None if observation is None else observation.get('depth')
-        if depth is not None and self._single:
-            depth = np.asarray(depth, np.float32).reshape((1,) + np.shape(depth)[-2:])
-        cand = v.sample_antipodal_candidates(self.num_samples, depth, self.config)
-        if self._single and int(v.antipodal_status[0].item()) != 1:
-            raise ValueError('Failed to sample any valid grasp (antipodal status %d).' % int(v.antipodal_status[0].item()))
+        cand = self._sample(self._depth_of(observation, render=False))      # (no depth: the sampler renders)
         rewards, _ = v.try_grasps(v.antipodal_actions4)
-        k = self.num_samples
-        index = t.arange(k, device=v.device)[None, :].expand(v.num_envs, k)
-        first = t.where(rewards > 0, index, t.full_like(index, k)).min(dim=1).values      # (the lowest index that succeeds)
-        choice = t.where(first < k, first, t.zeros_like(first))
+        choice = self._first_index(rewards > 0)      # (the lowest index that succeeds)
         self.last_choice, self.last_rewards = choice, rewards
         actions = cand[t.arange(v.num_envs, device=v.device), choice]
         if self._single:
@@ -100,7 +125,7 @@ class LookaheadGrasp4DofPolicy(Policy):
         return actions
 
 
-class GraspQualityPolicy(Policy):
+class GraspQualityPolicy(_GraspCandidatePolicy):
     """AntipodalGrasp4DofPolicy with a learned ranking in place of "the first one": ``num_samples`` distinct antipodal
     grasps per env (``sample_antipodal_candidates``) from one depth image, their grasp-centred crops and the logits of
     ``model`` (``grasp_qualities``: rv_grasp_crops, rv_grasp_quality), and the action is the candidate with the highest
@@ -112,12 +137,7 @@ class GraspQualityPolicy(Policy):
     ``VecGrasp4DofEnv`` or a ``Grasp4DofEnv``."""
 
     def __init__(self, env, model, num_samples, config=None, **crop):
-        config = config or configs.AttrDict(configs.ANTIPODAL_GRASP_4DOF_POLICY_CONFIG)
-        super(GraspQualityPolicy, self).__init__(env, config)
-        self._vec = getattr(env, '_vec', env)      # (a Grasp4DofEnv is a VecGrasp4DofEnv of one)
-        self._single = self._vec is not env
-        if not hasattr(self._vec, 'grasp_qualities'):
-            raise NotImplementedError('GraspQualityPolicy needs a Grasp4DofEnv / VecGrasp4DofEnv')
+        super(GraspQualityPolicy, self).__init__(env, config, 'grasp_qualities')
         self.model, self.crop = model, dict(crop)
         self.num_samples = int(num_samples)
         if self.num_samples < 1:
@@ -127,22 +147,14 @@ class GraspQualityPolicy(Policy):
     def _action(self, observation):
         v = self._vec
         t = v.world.torch
-        depth = None if observation is None else observation.get('depth')
-        if depth is not None and self._single:
-            depth = np.asarray(depth, np.float32).reshape((1,) + np.shape(depth)[-2:])
-        if depth is None:
-            depth, _ = v.world.render()      # (one render serves the sampler and the crops)
-        cand = v.sample_antipodal_candidates(self.num_samples, depth, self.config)
-        if self._single and int(v.antipodal_status[0].item()) != 1:
-            raise ValueError('Failed to sample any valid grasp (antipodal status %d).' % int(v.antipodal_status[0].item()))
+        depth = self._depth_of(observation, render=True)      # (one render serves the sampler and the crops)
+        cand = self._sample(depth)
         logits = v.grasp_qualities(self.model, v.antipodal_image_grasps, depth, **self.crop)
-        k = self.num_samples
-        index = t.arange(k, device=v.device)[None, :].expand(v.num_envs, k)
+        index = t.arange(self.num_samples, device=v.device)[None, :]
         valid = (v.antipodal_status == 1)[:, None] & (index < v.antipodal_count[:, None])
         masked = t.where(valid, logits, t.full_like(logits, float('-inf')))
         best = masked.max(dim=1, keepdim=True).values      # (NaN if a valid logit is NaN; -inf without a valid row)
-        first = t.where(valid & (masked == best), index, t.full_like(index, k)).min(dim=1).values
-        choice = t.where(first < k, first, t.zeros_like(first))      # (NaN equals nothing: candidate 0)
+        choice = self._first_index(valid & (masked == best))      # (NaN equals nothing: candidate 0)
         self.last_choice, self.last_logits = choice, logits
         actions = cand[t.arange(v.num_envs, device=v.device), choice]
         if self._single:
@@ -151,7 +163,7 @@ class GraspQualityPolicy(Policy):
         return actions
 
 
-class CEMGraspPolicy(Policy):
+class CEMGraspPolicy(_GraspCandidatePolicy):
     """``GraspQualityPolicy`` with a search around the good candidates: one render, ``num_samples`` (K)
     antipodal candidates (``sample_antipodal_candidates``), then ``num_iterations`` times { score; ``refine_grasps``: keep
     the ``num_elites`` best, resample the rest around them } with the sigmas times ``decay ** t`` in round t, and a final
@@ -172,12 +184,7 @@ class CEMGraspPolicy(Policy):
 
     def __init__(self, env, num_samples, num_iterations=2, num_elites=None, model=None, score='model', sigma_center=3.0,
                  sigma_angle=0.15, sigma_depth=0.005, decay=0.5, seed=0, config=None, **crop):
-        config = config or configs.AttrDict(configs.ANTIPODAL_GRASP_4DOF_POLICY_CONFIG)
-        super(CEMGraspPolicy, self).__init__(env, config)
-        self._vec = getattr(env, '_vec', env)      # (a Grasp4DofEnv is a VecGrasp4DofEnv of one)
-        self._single = self._vec is not env
-        if not hasattr(self._vec, 'refine_grasps'):
-            raise NotImplementedError('CEMGraspPolicy needs a Grasp4DofEnv / VecGrasp4DofEnv')
+        super(CEMGraspPolicy, self).__init__(env, config, 'refine_grasps')
         self.num_samples, self.num_iterations = int(num_samples), int(num_iterations)
         if self.num_samples < 1 or self.num_iterations < 0:
             raise ValueError('CEMGraspPolicy: num_samples must be positive and num_iterations not negative')
@@ -202,15 +209,8 @@ class CEMGraspPolicy(Policy):
     def _action(self, observation):
         v = self._vec
         t = v.world.torch
-        depth = None if observation is None else observation.get('depth')
-        if depth is not None and self._single:
-            depth = np.asarray(depth, np.float32).reshape((1,) + np.shape(depth)[-2:])
-        if depth is None:
-            depth, _ = v.world.render()      # (one render serves the sampler, the crops and the refinement)
-        first = v.sample_antipodal_candidates(self.num_samples, depth, self.config)
-        if self._single and int(v.antipodal_status[0].item()) != 1:
-            raise ValueError('Failed to sample any valid grasp (antipodal status %d).' % int(v.antipodal_status[0].item()))
-        first0 = first[:, 0].clone()
+        depth = self._depth_of(observation, render=True)      # (one render serves the sampler, the crops and the refinement)
+        first0 = self._sample(depth)[:, 0].clone()
         scores, parents = [], []
         for it in range(self.num_iterations):
             scores.append(self._scores(depth))
@@ -230,45 +230,36 @@ class CEMGraspPolicy(Policy):
         return actions
 
 
-class ShootingPushPolicy(Policy):
-    """Random-shooting model-predictive control with the simulator as the model: per env ``num_samples`` candidate
-    action sequences of ``horizon`` steps, drawn U(-1, 1) from a torch generator seeded with ``seed``, are tried on
-    copies of the env in one call (``VecPushEnv.simulate_plans``) and ranked -- by the planning-mode PushReward of the
-    simulated states (``score_plans``, discount ``gamma``; ``use_plan_reward=True``) or by the discounted sum of the
-    rewards the env itself gave along the way.  The action is the first one of the best sequence, the lowest index
-    among equals; the env does not change.  ``env``: a ``VecPushEnv`` or a ``PushEnv``."""
+class _LookaheadPushPolicy(Policy):
+    """What the look-ahead push policies share: the set-up, the ranking of simulated plans (``_rank``) and the first
+    action of the best one (``_first_actions``).  ``env``: a ``VecPushEnv`` or a ``PushEnv``."""
 
-    def __init__(self, env, num_samples, horizon, gamma=1.0, seed=0, use_plan_reward=True, is_high_level=False, config=None):
-        super(ShootingPushPolicy, self).__init__(env, config)
+    def __init__(self, env, config, num_samples, horizon, gamma, use_plan_reward, is_high_level):
+        super(_LookaheadPushPolicy, self).__init__(env, config)
         if int(num_samples) < 1 or int(horizon) < 1:
-            raise ValueError('ShootingPushPolicy: num_samples and horizon must be positive')
+            raise ValueError('%s: num_samples and horizon must be positive' % type(self).__name__)
         self._vec = getattr(env, '_vec', env)      # (a PushEnv is a VecPushEnv of one)
         self._single = self._vec is not env
         self.num_samples, self.horizon, self.gamma = int(num_samples), int(horizon), float(gamma)
         self.use_plan_reward, self.is_high_level = bool(use_plan_reward), bool(is_high_level)
         self._torch = self._vec.world.torch
-        self._gen = self._torch.Generator(device=self._vec.device)
-        self.reseed(seed)
-        self.last_best = self.last_returns = None
 
-    def reseed(self, seed):
-        """start the candidate stream over: the same seed gives the same candidates again"""
-        self._gen.manual_seed(int(seed))
-
-    def plan(self, observation=None):
-        """(actions [N] + action shape, best int32 [N]) -- for a PushEnv one action and an int.  Also kept:
-        ``last_best`` and ``last_returns`` [N, S]."""
+    def _rank(self, states, rewards):
+        """(returns [N, S], best int32 [N]): the planning-mode PushReward of ``states`` (``score_plans``, discount
+        ``gamma``) with ``use_plan_reward``, else the discounted sum of ``rewards`` [N, S, H]; the lowest index among
+        equals"""
         t, v = self._torch, self._vec
-        shape = (v.num_envs, self.num_samples, self.horizon) + tuple(v.action_shape)
-        cand = t.rand(shape, generator=self._gen, device=v.device, dtype=t.float32) * 2.0 - 1.0
-        states, rewards, _ = v.simulate_plans(cand)
         if self.use_plan_reward:
             returns, _, best = v.score_plans(states, None, self.is_high_level, self.gamma)
         else:
             disc = t.full((self.horizon,), self.gamma, device=v.device, dtype=t.float32) ** t.arange(self.horizon, device=v.device)
             returns = (rewards * disc).sum(dim=2)
             best = returns.argmax(dim=1).to(t.int32)      # (the first of equal maxima)
-        self.last_best, self.last_returns = best, returns
+        return returns, best
+
+    def _first_actions(self, cand, best):
+        """(step 0 of candidate ``best`` per env, ``best``) -- for a PushEnv one action and an int"""
+        t, v = self._torch, self._vec
         actions = cand[t.arange(v.num_envs, device=v.device), best.long(), 0]
         if self._single:
             return actions[0].cpu().numpy(), int(best[0])
@@ -277,8 +268,46 @@ class ShootingPushPolicy(Policy):
     def _action(self, observation):
         return self.plan(observation)[0]
 
+    def plan(self, observation=None):
+        """(actions [N] + action shape, best int32 [N]) -- for a PushEnv one action and an int.  Also kept:
+        ``last_best`` and ``last_returns`` [N, S] (and ``last_found`` where the candidates are proposals).  One round of
+        candidates from the policy's ``_candidates()`` -> (cand [N, S, H] + action shape, states, rewards, found or
+        None), ranked once."""
+        cand, states, rewards, found = self._candidates()
+        returns, best = self._rank(states, rewards)
+        self.last_best, self.last_returns = best, returns
+        if found is not None:
+            self.last_found = found
+        return self._first_actions(cand, best)
 
-class HeuristicShootingPushPolicy(Policy):
+
+class ShootingPushPolicy(_LookaheadPushPolicy):
+    """Random-shooting model-predictive control with the simulator as the model: per env ``num_samples`` candidate
+    action sequences of ``horizon`` steps, drawn U(-1, 1) from a torch generator seeded with ``seed``, are tried on
+    copies of the env in one call (``VecPushEnv.simulate_plans``) and ranked -- by the planning-mode PushReward of the
+    simulated states (``score_plans``, discount ``gamma``; ``use_plan_reward=True``) or by the discounted sum of the
+    rewards the env itself gave along the way.  The action is the first one of the best sequence, the lowest index
+    among equals; the env does not change.  ``env``: a ``VecPushEnv`` or a ``PushEnv``."""
+
+    def __init__(self, env, num_samples, horizon, gamma=1.0, seed=0, use_plan_reward=True, is_high_level=False, config=None):
+        super(ShootingPushPolicy, self).__init__(env, config, num_samples, horizon, gamma, use_plan_reward, is_high_level)
+        self._gen = self._torch.Generator(device=self._vec.device)
+        self.reseed(seed)
+        self.last_best = self.last_returns = None
+
+    def reseed(self, seed):
+        """start the candidate stream over: the same seed gives the same candidates again"""
+        self._gen.manual_seed(int(seed))
+
+    def _candidates(self):
+        t, v = self._torch, self._vec
+        shape = (v.num_envs, self.num_samples, self.horizon) + tuple(v.action_shape)
+        cand = t.rand(shape, generator=self._gen, device=v.device, dtype=t.float32) * 2.0 - 1.0
+        states, rewards, _ = v.simulate_plans(cand)
+        return cand, states, rewards, None
+
+
+class HeuristicShootingPushPolicy(_LookaheadPushPolicy):
     """``ShootingPushPolicy`` with informed candidates: per env ``num_samples`` plans of ``horizon`` aimed pushes
     (``VecPushEnv.propose_plans``: every push starts ``start_margin`` clear of the bodies and touches one of them within
     ``motion_margin``, candidate k aiming at body k % n_bodies, each step drawn from the simulated state its plan has
@@ -291,39 +320,18 @@ class HeuristicShootingPushPolicy(Policy):
 
     def __init__(self, env, num_samples, horizon, gamma=1.0, seed=0, max_attempts=20000, start_margin=0.05,
                  motion_margin=0.01, use_plan_reward=True, is_high_level=False, config=None):
-        super(HeuristicShootingPushPolicy, self).__init__(env, config)
-        if int(num_samples) < 1 or int(horizon) < 1:
-            raise ValueError('HeuristicShootingPushPolicy: num_samples and horizon must be positive')
-        self._vec = getattr(env, '_vec', env)      # (a PushEnv is a VecPushEnv of one)
-        self._single = self._vec is not env
-        self.num_samples, self.horizon, self.gamma, self.seed = int(num_samples), int(horizon), float(gamma), int(seed)
+        super(HeuristicShootingPushPolicy, self).__init__(env, config, num_samples, horizon, gamma, use_plan_reward, is_high_level)
+        self.seed = int(seed)
         self.max_attempts, self.start_margin, self.motion_margin = int(max_attempts), float(start_margin), float(motion_margin)
-        self.use_plan_reward, self.is_high_level = bool(use_plan_reward), bool(is_high_level)
-        self._torch = self._vec.world.torch
         self.last_best = self.last_returns = self.last_found = None
 
-    def plan(self, observation=None):
-        """(actions [N] + action shape, best int32 [N]) -- for a PushEnv one action and an int."""
-        t, v = self._torch, self._vec
-        cand, states, rewards, _, found = v.propose_plans(self.num_samples, self.horizon, self.seed, self.max_attempts,
-                                                          self.start_margin, self.motion_margin)
-        if self.use_plan_reward:
-            returns, _, best = v.score_plans(states, None, self.is_high_level, self.gamma)
-        else:
-            disc = t.full((self.horizon,), self.gamma, device=v.device, dtype=t.float32) ** t.arange(self.horizon, device=v.device)
-            returns = (rewards * disc).sum(dim=2)
-            best = returns.argmax(dim=1).to(t.int32)      # (the first of equal maxima)
-        self.last_best, self.last_returns, self.last_found = best, returns, found
-        actions = cand[t.arange(v.num_envs, device=v.device), best.long(), 0]
-        if self._single:
-            return actions[0].cpu().numpy(), int(best[0])
-        return actions, best
-
-    def _action(self, observation):
-        return self.plan(observation)[0]
+    def _candidates(self):
+        cand, states, rewards, _, found = self._vec.propose_plans(self.num_samples, self.horizon, self.seed, self.max_attempts,
+                                                                  self.start_margin, self.motion_margin)
+        return cand, states, rewards, found
 
 
-class RouteShootingPushPolicy(Policy):
+class RouteShootingPushPolicy(_LookaheadPushPolicy):
     """``HeuristicShootingPushPolicy`` with candidates that know the layout: per env ``num_samples`` plans of ``horizon``
     pushes that move body 0, the task's target, one cell along the tiles towards the goal
     (``VecPushEnv.propose_route_plans``: candidate 0 is the push without jitter, the others vary its direction, back-off,
@@ -337,38 +345,17 @@ class RouteShootingPushPolicy(Policy):
 
     def __init__(self, env, num_samples, horizon, gamma=1.0, seed=0, use_plan_reward=True, is_high_level=False, config=None,
                  **route):
-        super(RouteShootingPushPolicy, self).__init__(env, config)
-        if int(num_samples) < 1 or int(horizon) < 1:
-            raise ValueError('RouteShootingPushPolicy: num_samples and horizon must be positive')
-        self._vec = getattr(env, '_vec', env)      # (a PushEnv is a VecPushEnv of one)
-        self._single = self._vec is not env
-        self.num_samples, self.horizon, self.gamma, self.seed = int(num_samples), int(horizon), float(gamma), int(seed)
+        super(RouteShootingPushPolicy, self).__init__(env, config, num_samples, horizon, gamma, use_plan_reward, is_high_level)
+        self.seed = int(seed)
         self.route = dict(route)
-        self.use_plan_reward, self.is_high_level = bool(use_plan_reward), bool(is_high_level)
-        self._torch = self._vec.world.torch
         self.last_best = self.last_returns = self.last_found = None
 
-    def plan(self, observation=None):
-        """(actions [N] + action shape, best int32 [N]) -- for a PushEnv one action and an int."""
-        t, v = self._torch, self._vec
-        cand, states, rewards, _, found = v.propose_route_plans(self.num_samples, self.horizon, self.seed, **self.route)
-        if self.use_plan_reward:
-            returns, _, best = v.score_plans(states, None, self.is_high_level, self.gamma)
-        else:
-            disc = t.full((self.horizon,), self.gamma, device=v.device, dtype=t.float32) ** t.arange(self.horizon, device=v.device)
-            returns = (rewards * disc).sum(dim=2)
-            best = returns.argmax(dim=1).to(t.int32)      # (the first of equal maxima)
-        self.last_best, self.last_returns, self.last_found = best, returns, found
-        actions = cand[t.arange(v.num_envs, device=v.device), best.long(), 0]
-        if self._single:
-            return actions[0].cpu().numpy(), int(best[0])
-        return actions, best
-
-    def _action(self, observation):
-        return self.plan(observation)[0]
+    def _candidates(self):
+        cand, states, rewards, _, found = self._vec.propose_route_plans(self.num_samples, self.horizon, self.seed, **self.route)
+        return cand, states, rewards, found
 
 
-class CEMPushPolicy(Policy):
+class CEMPushPolicy(_LookaheadPushPolicy):
     """Cross-entropy-method model-predictive control with the simulator as the model.  Per env a normal distribution over
     action sequences of ``horizon`` steps starts at mean 0, std ``init_std``; ``num_iterations`` times, ``num_samples``
     candidates are drawn from it on the device (``VecPushEnv.sample_plan_candidates``: Philox keyed by the world's seed,
@@ -384,19 +371,15 @@ class CEMPushPolicy(Policy):
 
     def __init__(self, env, num_samples, horizon, num_iterations=3, num_elites=None, gamma=1.0, init_std=0.5, min_std=0.05,
                  alpha=0.0, seed=0, keep_mean=True, warm_start=True, use_plan_reward=True, is_high_level=False, config=None):
-        super(CEMPushPolicy, self).__init__(env, config)
         if int(num_samples) < 1 or int(horizon) < 1 or int(num_iterations) < 1:
             raise ValueError('CEMPushPolicy: num_samples, horizon and num_iterations must be positive')
-        self._vec = getattr(env, '_vec', env)      # (a PushEnv is a VecPushEnv of one)
-        self._single = self._vec is not env
-        self.num_samples, self.horizon, self.num_iterations = int(num_samples), int(horizon), int(num_iterations)
+        super(CEMPushPolicy, self).__init__(env, config, num_samples, horizon, gamma, use_plan_reward, is_high_level)
+        self.num_iterations = int(num_iterations)
         self.num_elites = max(1, self.num_samples // 8) if num_elites is None else int(num_elites)
         if not 1 <= self.num_elites <= self.num_samples:
             raise ValueError('CEMPushPolicy: num_elites must be in [1, num_samples]')
-        self.gamma, self.init_std, self.min_std, self.alpha = float(gamma), float(init_std), float(min_std), float(alpha)
+        self.init_std, self.min_std, self.alpha = float(init_std), float(min_std), float(alpha)
         self.seed, self.keep_mean, self.warm_start = int(seed), bool(keep_mean), bool(warm_start)
-        self.use_plan_reward, self.is_high_level = bool(use_plan_reward), bool(is_high_level)
-        self._torch = self._vec.world.torch
         self._warm = None      # the next call's initial mean, [N, H] + action shape
         self.last_mean = self.last_std = self.last_returns = self.last_best = None
 
@@ -430,12 +413,7 @@ class CEMPushPolicy(Policy):
         for it in range(self.num_iterations):
             cand = v.sample_plan_candidates(mean, std, self.num_samples, it, self.seed, self.keep_mean)
             states, rewards, _ = v.simulate_plans(cand)
-            if self.use_plan_reward:
-                returns, _, best = v.score_plans(states, None, self.is_high_level, self.gamma)
-            else:
-                disc = t.full((self.horizon,), self.gamma, device=v.device, dtype=t.float32) ** t.arange(self.horizon, device=v.device)
-                returns = (rewards * disc).sum(dim=2)
-                best = returns.argmax(dim=1).to(t.int32)      # (the first of equal maxima)
+            returns, best = self._rank(states, rewards)
             val, act = returns[rows, best.long()], cand[rows, best.long(), 0]
             if it == 0:
                 best_val, best_idx, best_act = val, best, act
@@ -456,6 +434,3 @@ class CEMPushPolicy(Policy):
             self.last_best = (int(best_it[0]), int(best_idx[0]))
             return best_act[0].cpu().numpy(), self.last_best
         return best_act, self.last_best
-
-    def _action(self, observation):
-        return self.plan(observation)[0]

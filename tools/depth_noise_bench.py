@@ -19,25 +19,10 @@ import sys
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
 
-import numpy as np
 import torch
 
 from robovat_amd import configs, lib, scenes
-
-
-def alternate(fns, iters, warmup):
-    """median / min / max device ms of every fn, called in turn so that all see the same machine"""
-    for _ in range(warmup):
-        for fn in fns.values():
-            fn()
-    torch.cuda.synchronize()
-    times = dict((k, []) for k in fns)
-    for _ in range(iters):
-        for name, fn in fns.items():
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record(); fn(); b.record(); b.synchronize()
-            times[name].append(a.elapsed_time(b))
-    return dict((k, (float(np.median(v)), float(np.min(v)), float(np.max(v)))) for k, v in times.items())
+from benchlib import alternate
 
 
 def torch_noise(depth, out, shape, prob, r, sigma, gen):

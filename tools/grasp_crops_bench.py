@@ -29,23 +29,9 @@ import torch
 
 from robovat_amd import lib
 from robovat_amd.envs.grasp.grasp_4dof_env import VecGrasp4DofEnv
+from benchlib import alternate
 
 SHAPES = [(32, 32, 3), (96, 96, 1)]
-
-
-def alternate(fns, iters, warmup):
-    """median / min / max device ms of every fn, called in turn so that all see the same machine"""
-    for _ in range(warmup):
-        for fn in fns.values():
-            fn()
-    torch.cuda.synchronize()
-    times = dict((k, []) for k in fns)
-    for _ in range(iters):
-        for name, fn in fns.items():
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record(); fn(); b.record(); b.synchronize()
-            times[name].append(a.elapsed_time(b))
-    return dict((k, (float(np.median(v)), float(np.min(v)), float(np.max(v)))) for k, v in times.items())
 
 
 def torch_crops(depth, grasps, h, w, step):

@@ -30,32 +30,9 @@ import torch
 from robovat_amd import configs, lib, policies
 from robovat_amd.envs.grasp.grasp_4dof_env import VecGrasp4DofEnv
 from robovat_amd.perception.grasp_quality import GraspQualityModel
+from benchlib import alternate, wall
 
 SIGMAS = (3.0, 0.15, 0.005)
-
-
-def alternate(fns, iters, warmup):
-    """median / min / max device ms of every fn, called in turn so that all see the same machine"""
-    for _ in range(warmup):
-        for fn in fns.values():
-            fn()
-    torch.cuda.synchronize()
-    times = dict((k, []) for k in fns)
-    for _ in range(iters):
-        for name, fn in fns.items():
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record(); fn(); b.record(); b.synchronize()
-            times[name].append(a.elapsed_time(b))
-    return dict((k, (float(np.median(v)), float(np.min(v)), float(np.max(v)))) for k, v in times.items())
-
-
-def wall(fn, reps=3):
-    fn(); torch.cuda.synchronize()
-    out = []
-    for _ in range(reps):
-        t0 = time.perf_counter(); fn(); torch.cuda.synchronize()
-        out.append(time.perf_counter() - t0)
-    return float(np.median(out))
 
 
 def torch_step(depth, grasps, scores, count, status, cam, n_elites, sigmas, sampler):

@@ -23,29 +23,10 @@ import sys
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
 
-import numpy as np
 import torch
 
 from robovat_amd import configs, lib, scenes
-
-GAMMA = 0.9
-# (CEM iterations, CEM samples, horizon): shooting and the heuristic proposals get iterations x samples candidates
-BUDGETS = ((4, 16, 2), (4, 32, 4))
-
-
-def alternate(fns, iters, warmup):
-    """median / min / max device ms of every fn, called in turn so that all see the same machine"""
-    for _ in range(warmup):
-        for fn in fns.values():
-            fn()
-    torch.cuda.synchronize()
-    times = dict((k, []) for k in fns)
-    for _ in range(iters):
-        for name, fn in fns.items():
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record(); fn(); b.record(); b.synchronize()
-            times[name].append(a.elapsed_time(b))
-    return dict((k, (float(np.median(v)), float(np.min(v)), float(np.max(v)))) for k, v in times.items())
+from benchlib import alternate, rate_line, run_episodes, BUDGETS, GAMMA
 
 
 def torch_proposals(pos, mask, s, attempts, cfg, start_margin, motion_margin, gen):
@@ -108,46 +89,20 @@ def kernels(say, n, s, attempts, iters, warmup):
         w.close()
 
 
-def make_policy(name, env, budget):
-    from robovat_amd import policies
-    it, s, h = budget
-    if name == 'heuristic':
-        return policies.HeuristicShootingPushPolicy(env, it * s, h, gamma=GAMMA, seed=1)
-    if name == 'cem':
-        return policies.CEMPushPolicy(env, s, h, num_iterations=it, gamma=GAMMA, seed=1)
-    if name == 'shooting':
-        return policies.ShootingPushPolicy(env, it * s, h, gamma=GAMMA, seed=1)
-    return policies.RandomPolicy(env)
-
-
 def goal_rate(say, budget, n=64, max_steps=8):
-    from robovat_amd.envs.push.push_env import VecPushEnv
     it, s, h = budget
     cfg = configs.push_env_config(TASK_NAME='crossing', LAYOUT_ID=0, MAX_STEPS=max_steps)
     say('--- crossing layout 0, %d envs, seed 5, one episode each of at most %d steps, gamma %.1f; %d simulated candidate steps per'
         ' decision: HeuristicShootingPushPolicy and ShootingPushPolicy S = %d, H = %d; CEMPushPolicy I = %d, S = %d, H = %d'
         ' (defaults otherwise)' % (n, max_steps, GAMMA, it * s * h, it * s, h, it, s, h))
     for name in ('heuristic', 'shooting', 'cem', 'random'):
-        env = VecPushEnv(n, config=cfg, seed=5)
-        try:
-            env.reset()
-            policy = make_policy(name, env, budget)
-            wins = done_eps = steps = ineffective = useful = 0
-            found = total = 0
-            for _ in range(max_steps):
-                env.step(policy.action(None))
-                st = env.stats()
-                wins += st['successes']; done_eps += st['episodes_done']
-                steps += st['env_steps']; ineffective += st['ineffective']; useful += st['useful']
-                if name == 'heuristic':
-                    found += int(policy.last_found.sum()); total += policy.last_found.numel()
-            extra = '' if name != 'heuristic' else '; proposals found within max_attempts: %.2f %%' % (100.0 * found / max(total, 1))
-            say('  %-9s policy: %d of %d episodes reached the goal (%.1f %%), %d episodes ended, mean episode return %.2f;'
-                ' %d env steps, effective %.1f %%, useful %.1f %%%s'
-                % (name, wins, n, 100.0 * wins / n, done_eps, float(env.world.episode_returns().mean()), steps,
-                   100.0 * (steps - ineffective) / max(steps, 1), 100.0 * useful / max(steps, 1), extra))
-        finally:
-            env.close()
+        found = [0, 0]      # proposals found, proposals made
+
+        def count(policy):
+            found[0] += int(policy.last_found.sum()); found[1] += policy.last_found.numel()
+        c = run_episodes(name, cfg, budget, GAMMA, n, max_steps, count if name == 'heuristic' else None)
+        extra = '' if name != 'heuristic' else '; proposals found within max_attempts: %.2f %%' % (100.0 * found[0] / max(found[1], 1))
+        say(rate_line(name, c, n, extra))
 
 
 def main():

@@ -21,13 +21,12 @@ import os
 import sys
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import numpy as np
 import torch
 
 from robovat_amd import abi, configs, lib, scenes
-from push_proposals_bench import alternate, make_policy, BUDGETS, GAMMA
+from benchlib import alternate, rate_line, run_episodes, BUDGETS, GAMMA
 
 
 def walkable(cfg):
@@ -125,41 +124,20 @@ def kernels(say, n, s, attempts, iters, warmup):
         w.close()
 
 
-def policy_of(name, env, budget):
-    from robovat_amd import policies
-    it, s, h = budget
-    if name == 'route':
-        return policies.RouteShootingPushPolicy(env, it * s, h, gamma=GAMMA, seed=1)
-    return make_policy(name, env, budget)
-
-
 def goal_rate(say, layout, budget, names, n=64, max_steps=8):
-    from robovat_amd.envs.push.push_env import VecPushEnv
     it, s, h = budget
     cfg = configs.push_env_config(TASK_NAME='crossing', LAYOUT_ID=layout, MAX_STEPS=max_steps)
     say('--- crossing layout %d, %d envs, seed 5, one episode each of at most %d steps, gamma %.1f; %d simulated candidate steps per'
         ' decision: Route-, Heuristic- and ShootingPushPolicy S = %d, H = %d; CEMPushPolicy I = %d, S = %d, H = %d'
         ' (defaults otherwise)' % (layout, n, max_steps, GAMMA, it * s * h, it * s, h, it, s, h))
     for name in names:
-        env = VecPushEnv(n, config=cfg, seed=5)
-        try:
-            env.reset()
-            policy = policy_of(name, env, budget)
-            wins = done_eps = steps = ineffective = useful = nominal = decisions = 0
-            for _ in range(max_steps):
-                env.step(policy.action(None))
-                st = env.stats()
-                wins += st['successes']; done_eps += st['episodes_done']
-                steps += st['env_steps']; ineffective += st['ineffective']; useful += st['useful']
-                if name == 'route':
-                    nominal += int((policy.last_best == 0).sum()); decisions += int(policy.last_best.numel())
-            extra = '' if name != 'route' else '; decisions that took the nominal candidate: %.1f %%' % (100.0 * nominal / max(decisions, 1))
-            say('  %-9s policy: %d of %d episodes reached the goal (%.1f %%), %d episodes ended, mean episode return %.2f;'
-                ' %d env steps, effective %.1f %%, useful %.1f %%%s'
-                % (name, wins, n, 100.0 * wins / n, done_eps, float(env.world.episode_returns().mean()), steps,
-                   100.0 * (steps - ineffective) / max(steps, 1), 100.0 * useful / max(steps, 1), extra))
-        finally:
-            env.close()
+        nominal = [0, 0]      # decisions that took candidate 0, decisions
+
+        def count(policy):
+            nominal[0] += int((policy.last_best == 0).sum()); nominal[1] += int(policy.last_best.numel())
+        c = run_episodes(name, cfg, budget, GAMMA, n, max_steps, count if name == 'route' else None)
+        extra = '' if name != 'route' else '; decisions that took the nominal candidate: %.1f %%' % (100.0 * nominal[0] / max(nominal[1], 1))
+        say(rate_line(name, c, n, extra))
 
 
 def main():
