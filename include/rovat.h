@@ -344,7 +344,8 @@ int  rv_rollout(rv_world* w, int32_t n_steps, int32_t first_macro_index, int32_t
  * slowest env of every batched env.step() (robot_env.py:239-275; the reference's worker
  * processes are just as independent, tools/parallel_run.py:54-90).  rv_step_begin gives the envs
  * flagged in d_mask (NULL: all) their next action ([N][G][4]); rv_step_poll advances every env
- * that is in the middle of a step by at most max_substeps Simulator.step() calls and / or about
+ * that is in the middle of a step by at most max_substeps Simulator.step() calls (one more when a coasting run of the
+ * arm ends on the budget: the regular substep it stopped at is still taken) and / or about
  * max_usec microseconds of GPU time (0 = no limit) and sets d_finished[i] = 1 for the envs whose
  * env.step() completed in this launch; for those envs -- and only those -- row i of the optional
  * obs / d_reward / d_done ([N] rows, as rv_observe / rv_reward lay them out) receives what
@@ -943,6 +944,31 @@ int  rv_render(rv_world* w, float* d_depth /* [N][cam_height][cam_width] */, uin
  * one fixed directional light (BUILD-CHOSEN colours: the reference draws random rgba per body,
  * push_env.py:436).  The arm's link boxes are drawn in a flat grey. */
 int  rv_render_rgb(rv_world* w, uint8_t* d_rgb /* [N][cam_height][cam_width][3] */);
+/* ---- Free camera views of chosen envs (no counterpart in the reference's observation path; its PushEnv draws a second,
+ *      "recording" camera through pybullet, push_env.py:282-327, 1155-1162).  View v looks at env h_env_index[v] through
+ *      camera row v of h_cameras -- the layout of rv_get_camera: fx, fy, cx, cy, skew, rotation[9] row-major,
+ *      translation[3] -- at height x width pixels: V images of any size from any pose, of any subset of the envs (an env
+ *      may be looked at by several views).  Pixel (u, v) of a view is what rv_render / rv_render_rgb compute for that env
+ *      with the camera of its snapshot replaced by the row: views that repeat the envs' own cameras at the config's size
+ *      reproduce those two bit for bit.  Depth 0, segmask 255 and the background colour where nothing is hit beyond
+ *      cam_near.  Any output pointer may be NULL, not all three.
+ *      supersample = s in 1..4 (rgb only): the host scales the row to the s-times larger image in float32 -- fx' = s fx,
+ *      fy' = s fy, skew' = s skew, cx' = s cx + (s - 1) / 2, cy' = s cy + (s - 1) / 2 -- and output pixel (u, v) is the
+ *      integer box filter (sum + s s / 2) / (s s), per channel, of the s x s pixels (s u + i, s v + j) of that image.
+ *      h_params, h_env_index and h_cameras are HOST arrays: everything is checked before anything is launched
+ *      (RV_ERR_VALUE, outputs untouched: a NULL among them, no output, n_views / height / width outside [1,
+ *      RV_VIEW_MAX_VIEWS / RV_VIEW_MAX_SIDE], supersample outside [1, RV_VIEW_MAX_SUPERSAMPLE], an env index outside
+ *      [0, N), a row with a non-finite entry or fx == 0 / fy == 0, d_depth not 4-byte aligned, depth or segmask with
+ *      s > 1) and then copied to a buffer of the world on its stream; the arrays may be reused on return.  The call reads
+ *      the envs only: it changes no env state and leaves a pending rv_step_begin / rv_step_poll step pending. */
+#define RV_VIEW_MAX_VIEWS 4096
+#define RV_VIEW_MAX_SIDE 4096
+#define RV_VIEW_MAX_SUPERSAMPLE 4
+typedef struct rv_view_params { int32_t n_views, height, width, supersample; } rv_view_params;
+int  rv_render_view(rv_world* w, const rv_view_params* h_params,
+                    const int32_t* h_env_index /* [V] */, const float* h_cameras /* [V][17] */,
+                    uint8_t* d_rgb /* [V][height][width][3] or NULL */, float* d_depth /* [V][height][width] or NULL */,
+                    uint8_t* d_segmask /* [V][height][width] or NULL */);
 
 /* ---- PushReward.get_reward (push_reward.py:377-405, 272-374) of the last
  *      macro step, and RobotEnv done flag (robot_env.py:257-259). ---- */

@@ -378,6 +378,23 @@ GRASP_REFINE_API = {
 }
 
 
+RV_VIEW_MAX_VIEWS = 4096
+RV_VIEW_MAX_SIDE = 4096
+RV_VIEW_MAX_SUPERSAMPLE = 4
+
+
+class rv_view_params(C.Structure):
+    _fields_ = [('n_views', i32), ('height', i32), ('width', i32), ('supersample', i32)]
+
+
+# rv_render_view (include/rovat.h): world, h_params, h_env_index, h_cameras, d_rgb, d_depth, d_segmask; lib.load() binds it
+# from here
+VIEW_API = {
+    'rv_render_view': (C.c_int, [C.c_void_p, C.POINTER(rv_view_params), C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
+
 def bind_state_api(handle):
     """restype / argtypes of the STATE_API functions on a loaded librovat_hip.so"""
     for name, (res, args) in STATE_API.items():

@@ -40,6 +40,7 @@
 #include "rv_dev_depth_noise.h"
 #include "rv_dev_push_sampler.h"
 #include "rv_dev_push_route.h"
+#include "rv_dev_view.h"
 
 using namespace rv;
 
@@ -608,6 +609,9 @@ struct rv_world {
   // rv_get_route_field / rv_policy_route_multi: D[64] and walkable[64] of the config's tiles (rv_dev_push_route.h), made at
   // first use -- no setter changes the tile fields of cfg after rv_create
   uint8_t* d_route;
+  // rv_render_view: [V] env indices then [V][17] camera rows, on the device and in pinned host memory (what was uploaded
+  // last: an identical call skips the copy); ev_view: the last upload has left the pinned copy
+  uint8_t* d_view; uint8_t* h_view; size_t view_cap, view_bytes; hipEvent_t ev_view;
 };
 
 static thread_local std::string g_err;
@@ -827,6 +831,7 @@ int rv_create(const rv_config* cfg, const rv_scene* scene, int device, rv_world*
   w->d_ap_depth = nullptr; w->ap_depth_cap = 0; w->d_ap_scratch = nullptr; w->ap_scratch_cap = 0;
   w->d_dn_scratch = nullptr; w->dn_scratch_cap = 0;
   w->d_route = nullptr;
+  w->d_view = nullptr; w->h_view = nullptr; w->view_cap = 0; w->view_bytes = 0;
   w->scene_hash = bytes_hash(scene, sizeof(rv_scene));
   {
     // one wave per env: with more envs than SIMDs the two-waves-per-SIMD build of the env kernel pays
@@ -856,6 +861,7 @@ int rv_create(const rv_config* cfg, const rv_scene* scene, int device, rv_world*
   HIPCHK(hipEventCreate(&w->ev0));
   HIPCHK(hipEventCreate(&w->ev1));
   HIPCHK(hipEventCreateWithFlags(&w->ev_state, hipEventDisableTiming));
+  HIPCHK(hipEventCreateWithFlags(&w->ev_view, hipEventDisableTiming));
   hipLaunchKernelGGL(k_init, grid1(w->n), dim3(TPB), 0, w->stream, w->d_envs, w->n, cfg->arm_friction, cfg->table_friction, w->d_cfg);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(w->stream));
@@ -874,7 +880,9 @@ int rv_destroy(rv_world* w) {
   if (w->d_ap_scratch) (void)hipFree(w->d_ap_scratch);
   if (w->d_dn_scratch) (void)hipFree(w->d_dn_scratch);
   if (w->d_route) (void)hipFree(w->d_route);
-  (void)hipEventDestroy(w->ev0); (void)hipEventDestroy(w->ev1); (void)hipEventDestroy(w->ev_state);
+  if (w->d_view) (void)hipFree(w->d_view);
+  if (w->h_view) (void)hipHostFree(w->h_view);
+  (void)hipEventDestroy(w->ev0); (void)hipEventDestroy(w->ev1); (void)hipEventDestroy(w->ev_state); (void)hipEventDestroy(w->ev_view);
   delete w;
   return RV_OK;
 }
@@ -1157,6 +1165,70 @@ int rv_render(rv_world* w, float* d_depth, uint8_t* d_segmask) {
   SIMPLE_LAUNCH(k_obs_snap, w->d_envs, w->n, w->d_snaps, w->d_scene);
   const size_t total = (size_t)w->n * (size_t)w->cfg.cam_height * (size_t)w->cfg.cam_width;
   hipLaunchKernelGGL(k_render, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, w->stream, w->d_snaps, w->n, d_depth, d_segmask, w->d_cfg, w->d_scene);
+  HIPCHK(hipGetLastError());
+  return RV_OK;
+}
+int rv_render_view(rv_world* w, const rv_view_params* p, const int32_t* h_env_index, const float* h_cameras,
+                   uint8_t* d_rgb, float* d_depth, uint8_t* d_segmask) {
+  WCHK(w);
+  if (!p || !h_env_index || !h_cameras) return fail(RV_ERR_VALUE, "rv_render_view: null params, env index or cameras");
+  if (!d_rgb && !d_depth && !d_segmask) return fail(RV_ERR_VALUE, "rv_render_view: no output buffer");
+  if (p->n_views < 1 || p->n_views > RV_VIEW_MAX_VIEWS) return fail(RV_ERR_VALUE, "rv_render_view: n_views outside [1, RV_VIEW_MAX_VIEWS]");
+  if (p->height < 1 || p->height > RV_VIEW_MAX_SIDE || p->width < 1 || p->width > RV_VIEW_MAX_SIDE)
+    return fail(RV_ERR_VALUE, "rv_render_view: height or width outside [1, RV_VIEW_MAX_SIDE]");
+  if (p->supersample < 1 || p->supersample > RV_VIEW_MAX_SUPERSAMPLE) return fail(RV_ERR_VALUE, "rv_render_view: supersample outside [1, RV_VIEW_MAX_SUPERSAMPLE]");
+  if (p->supersample > 1 && (d_depth || d_segmask)) return fail(RV_ERR_VALUE, "rv_render_view: supersampling is for rgb only (no depth or segmask with supersample > 1)");
+  if (d_depth && !aligned_to(d_depth, 4)) return fail(RV_ERR_VALUE, "rv_render_view: d_depth must be 4-byte aligned");
+  const size_t V = (size_t)p->n_views;
+  for (size_t k = 0; k < V; ++k) {
+    if (h_env_index[k] < 0 || h_env_index[k] >= w->n) return fail(RV_ERR_VALUE, "rv_render_view: env index " + std::to_string(h_env_index[k]) + " of view " + std::to_string(k) + " outside [0, N)");
+    const float* r = h_cameras + k * 17;
+    for (int j = 0; j < 17; ++j)      // (x - x is 0 for a finite x and NaN otherwise)
+      if (!(r[j] - r[j] == 0.0f)) return fail(RV_ERR_VALUE, "rv_render_view: camera row " + std::to_string(k) + " has a non-finite entry");
+    if (r[0] == 0.0f || r[1] == 0.0f) return fail(RV_ERR_VALUE, "rv_render_view: camera row " + std::to_string(k) + " has fx == 0 or fy == 0");
+  }
+  // the indices and the rows (scaled to the supersampled image, in float32) as one block: [V] int32, [V][17] float
+  const size_t bytes = V * sizeof(int32_t) + V * 17 * sizeof(float);
+  if (w->view_cap < bytes) {
+    HIPCHK(hipStreamSynchronize(w->stream));
+    if (w->d_view) { HIPCHK(hipFree(w->d_view)); w->d_view = nullptr; }
+    if (w->h_view) { HIPCHK(hipHostFree(w->h_view)); w->h_view = nullptr; }
+    w->view_cap = 0; w->view_bytes = 0;
+    HIPCHK(hipMalloc(&w->d_view, bytes));
+    HIPCHK(hipHostMalloc(&w->h_view, bytes, hipHostMallocDefault));
+    w->view_cap = bytes;
+  }
+  std::vector<uint8_t> block(bytes);
+  {
+    int32_t* idx = reinterpret_cast<int32_t*>(block.data());
+    float* rows = reinterpret_cast<float*>(block.data() + V * sizeof(int32_t));
+    const float s = (float)p->supersample, off = 0.5f * (float)(p->supersample - 1);
+    for (size_t k = 0; k < V; ++k) {
+      idx[k] = h_env_index[k];
+      const float* r = h_cameras + k * 17; float* o = rows + k * 17;
+      for (int j = 0; j < 17; ++j) o[j] = r[j];
+      if (p->supersample > 1) { o[0] = s * r[0]; o[1] = s * r[1]; o[4] = s * r[4]; o[2] = s * r[2] + off; o[3] = s * r[3] + off; }
+    }
+  }
+  if (w->view_bytes != bytes || memcmp(w->h_view, block.data(), bytes) != 0) {
+    if (w->view_bytes) HIPCHK(hipEventSynchronize(w->ev_view));      // the previous upload still reads the pinned copy
+    w->view_bytes = 0;
+    memcpy(w->h_view, block.data(), bytes);
+    HIPCHK(hipMemcpyAsync(w->d_view, w->h_view, bytes, hipMemcpyHostToDevice, w->stream));
+    HIPCHK(hipEventRecord(w->ev_view, w->stream));
+    w->view_bytes = bytes;
+  }
+  int rc = ensure_snaps(w, (size_t)w->n); if (rc != RV_OK) return rc;
+  SIMPLE_LAUNCH(k_obs_snap, w->d_envs, w->n, w->d_snaps, w->d_scene);
+  ViewArgs a;
+  a.snaps = w->d_snaps; a.env_index = reinterpret_cast<const int32_t*>(w->d_view);
+  a.cameras = reinterpret_cast<const float*>(w->d_view + V * sizeof(int32_t));
+  a.height = p->height; a.width = p->width; a.ss = p->supersample;
+  a.rgb = d_rgb; a.depth = d_depth; a.seg = d_segmask;
+  const size_t per_view = (size_t)p->height * (size_t)p->width;
+  const size_t per_group = (size_t)RV_VIEW_TPB * RV_VIEW_PPT;
+  hipLaunchKernelGGL(k_render_view, dim3((unsigned)((per_view + per_group - 1) / per_group), (unsigned)V), dim3(RV_VIEW_TPB), 0, w->stream,
+                     a, w->d_cfg, w->d_scene);
   HIPCHK(hipGetLastError());
   return RV_OK;
 }

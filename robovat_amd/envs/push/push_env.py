@@ -63,6 +63,8 @@ class VecPushEnv(object):
         self.action_space = Box(-1.0, 1.0, self.action_shape)
         self._macro_index = 0
         self._plan_worlds = {}      # S -> the world of N x S envs that simulate_plans branches into
+        from robovat_amd.envs import recording
+        self._recorder = recording.make_recorder(self)      # config.RECORDING (None: off, the default)
 
     @property
     def device(self):
@@ -85,10 +87,29 @@ class VecPushEnv(object):
         self.world.reset(mask)
         if self._physics is not None:
             self._physics.on_env_reset()
+        if self._recorder is not None:
+            self._recorder.on_reset(mask)
         return self.get_observation()
 
     def step(self, actions):
-        """RobotEnv.step for every env whose episode is not done."""
+        """RobotEnv.step for every env whose episode is not done.  With ``config.RECORDING.USE`` the step goes through
+        ``record_step`` and the frames of the recorded envs go to their episode files (``envs/recording.py``)."""
+        if self._recorder is not None:
+            return self._recorder.step(actions)
+        return self._plain_step(actions)
+
+    def _world_actions(self, actions):
+        """the actions as the world takes them: float32 [N, G, 4] on the device"""
+        return self.world._in(actions, (self.num_envs, self.world.G, 4), self.world.torch.float32)
+
+    def record_step(self, actions, cameras, env_index, every, height=None, width=None, supersample=1, max_frames=256):
+        """``step(actions)`` watched through free cameras (``envs.recording.record_step``): returns (obs, reward, done,
+        {'frames' uint8 [T, V, H, W, 3], 'sim_steps' int32 [T, V], 'num_frames'}) -- a frame of every view before the first
+        substep, then at most ``every`` (>= 2) substeps apart, and of the completed state.  The first three are ``step()``'s bit for bit."""
+        from robovat_amd.envs import recording
+        return recording.record_step(self, actions, cameras, env_index, every, height, width, supersample, max_frames)
+
+    def _plain_step(self, actions):
         self.world.set_actions(actions)
         self.world.step_macro()
         self._macro_index += 1
@@ -298,6 +319,10 @@ class VecPushEnv(object):
         return self.world.stats()
 
     def close(self):
+        from robovat_amd.envs import recording
+        if self._recorder is not None:
+            self._recorder.close()
+        recording.close_record_worlds(self)
         for w in self._plan_worlds.values():
             w.close()
         self._plan_worlds = {}
@@ -379,14 +404,26 @@ class PushEnv(object):
         if self._done:
             raise ValueError('The environment is done. Forget to reset?')
         action = np.asarray(action, dtype=np.float32).reshape((1,) + self._vec.action_shape)
-        obs, reward, done, _ = self._vec.step(action)
+        return self._took(self._vec.step(action))
+
+    def _took(self, out):
+        """the bookkeeping of one step of the batch of one; the fourth entry is passed through"""
+        obs, reward, done, info = out
         self._prev_obs_data, self._obs_data = self._obs_data, self._convert(obs)
         reward = float(reward[0].item())
         self._done = bool(done[0].item())
         self._episode_reward += reward
         if self._done:
             self._total_reward += self._episode_reward
-        return self._obs_data, reward, self._done, None
+        return self._obs_data, reward, self._done, info
+
+    def record_step(self, action, cameras, every, height=None, width=None, supersample=1, max_frames=256):
+        """``step(action)`` watched through ``cameras`` (``VecPushEnv.record_step`` for this env): the fourth entry is
+        {'frames' uint8 [T, V, H, W, 3], 'sim_steps' int32 [T, V], 'num_frames'}."""
+        if self._done:
+            raise ValueError('The environment is done. Forget to reset?')
+        action = np.asarray(action, dtype=np.float32).reshape((1,) + self._vec.action_shape)
+        return self._took(self._vec.record_step(action, cameras, [0], every, height, width, supersample, max_frames))
 
     def get_observation(self):
         return self._obs_data

@@ -99,3 +99,37 @@ class Camera(object):
             pose = self.pose
             points = np.asarray(pose.position).reshape(3, 1) + pose.matrix3 @ points
         return np.array(points.T)
+
+
+def camera_row(camera):
+    """The calibration of a ``Camera`` as the float32 row [17] of ``rv_get_camera`` / ``rv_render_view``: fx, fy, cx, cy,
+    skew, rotation (row-major), translation."""
+    k = np.asarray(camera.intrinsics, dtype=np.float64)
+    row = np.concatenate([[k[0, 0], k[1, 1], k[0, 2], k[1, 2], k[0, 1]],
+                          np.asarray(camera.rotation, dtype=np.float64).reshape(9),
+                          np.asarray(camera.translation, dtype=np.float64).reshape(3)])
+    return row.astype(np.float32)
+
+
+def look_at(eye, target, up=(0.0, 0.0, 1.0), height=480, width=640, fov_y_deg=45.0):
+    """A ``Camera`` of ``height`` x ``width`` pixels at ``eye`` (world frame) whose optical axis passes through ``target``:
+    camera z forward, x right, y down -- the image's down direction opposes ``up`` --, square pixels with the vertical
+    field of view ``fov_y_deg``, no skew, and the principal point at the centre of the image, ((width - 1) / 2,
+    (height - 1) / 2) in the pixel-centre coordinates the renders use (pixel (u, v) looks along K^-1 [u, v, 1]).
+    ValueError when ``eye`` and ``target`` coincide or ``up`` is parallel to the viewing direction."""
+    eye, target, up = (np.asarray(v, dtype=np.float64).reshape(3) for v in (eye, target, up))
+    z = target - eye
+    if not np.linalg.norm(z) > 0.0:
+        raise ValueError('look_at: eye and target coincide')
+    z = z / np.linalg.norm(z)
+    x = np.cross(z, up)
+    if not np.linalg.norm(x) > 1e-9 * max(np.linalg.norm(up), 1e-300):
+        raise ValueError('look_at: up is parallel to the viewing direction')
+    x = x / np.linalg.norm(x)
+    y = np.cross(z, x)
+    rot = np.stack([x, y, z])
+    if not 0.0 < float(fov_y_deg) < 180.0:
+        raise ValueError('look_at: fov_y_deg outside (0, 180)')
+    f = 0.5 * float(height) / np.tan(0.5 * np.radians(float(fov_y_deg)))
+    k = [[f, 0.0, 0.5 * (float(width) - 1.0)], [0.0, f, 0.5 * (float(height) - 1.0)], [0.0, 0.0, 1.0]]
+    return Camera(height=int(height), width=int(width), intrinsics=k, translation=-rot @ eye, rotation=rot)

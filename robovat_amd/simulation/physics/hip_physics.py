@@ -28,7 +28,8 @@ class HipPhysics(Physics):
     def __init__(self, time_step=1e-3, use_visualizer=False, worker_id=0, config=None, robot_config=None,
                  device=0, seed=0):
         if use_visualizer:
-            raise NotImplementedError('the HIP backend has no debug visualizer')
+            raise NotImplementedError('the HIP backend has no debug visualizer (World.render_view draws any camera view of chosen '
+                                      'envs, and the RECORDING option of the envs writes them as files)')
         self._env_config = config or configs.push_env_config()
         self._robot_config = robot_config or configs.sawyer_config()
         self._env_config.PHYSICS.TIME_STEP = time_step

@@ -34,6 +34,8 @@
 #                  duration from a profiler run of the kernel half, and its resources
 #   grasp_refine   tools/grasp_refine_bench.py: rv_grasp_refine against a torch restatement of the step and next to one
 #                  scoring, and the success rate of CEMGraspPolicy next to the other grasp policies; the kernel's resources
+#   render_view    tools/render_view_bench.py: rv_render_view next to rv_render_rgb, supersampling in rays per second, and
+#                  record_step next to a plain step(); the kernel's resources
 #   lanes          SQ_THREAD_CYCLES_VALU / SQ_ACTIVE_INST_VALU lane-utilisation pass (headline and no-deactivation)
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}; TAG=$1; shift
 O=$R/gpurun_out/$TAG; mkdir -p $O; cd $R
@@ -115,6 +117,12 @@ for STAGE in "$@"; do
       python tools/kernel_resources.py > $O/kernel_resources_all.txt 2>&1
       grep -h "^kernel\|grasp_refine" $O/kernel_resources_all.txt > $O/grasp_refine_kernel_resources.txt
       tail -30 $O/grasp_refine_bench.txt; cat $O/grasp_refine_kernel_resources.txt ;;
+    render_view)
+      timeout -k 10 900 python tools/render_view_bench.py --out $O/render_view_bench.txt > $O/render_view_bench.log 2>&1
+      echo "render_view rc=$?" >> $O/time.txt
+      python tools/kernel_resources.py > $O/kernel_resources_all.txt 2>&1
+      grep -h "^kernel\|render\|obs_snap" $O/kernel_resources_all.txt > $O/render_view_kernel_resources.txt
+      tail -30 $O/render_view_bench.txt; cat $O/render_view_kernel_resources.txt ;;
     lanes)
       cd /tmp
       for V in head nd; do
