@@ -507,6 +507,47 @@ typedef struct rv_grasp_quality_model { int32_t height, width, c1, c2, f1, f2, p
 int64_t rv_grasp_quality_weight_count(const rv_grasp_quality_model* h_model);
 int  rv_grasp_quality(rv_world* w, const rv_grasp_quality_model* h_model, const float* d_weights,
                       const float* d_images, const float* d_grasp_depths, int32_t k, float* d_logits);
+/* ---- a training step of that network on the device (csrc/rv_dev_grasp_train.h has it operation for operation;
+ *      DESIGN.md §24).  The loss stays with the caller: the forward entry returns logits, the caller computes
+ *      g[b] = dL/dlogit[b] (any loss; no exponential runs in a kernel) and hands it to the backward entry.  Unlike
+ *      rv_grasp_quality the batch size m is a parameter, 1 .. RV_GQ_MAX_BATCH, not the world's N x k.
+ *      rv_grasp_quality_train_workspace_floats: floats of workspace for m samples (about 57 KB per sample at the default
+ *      sizes), or -1 for a NULL or refused descriptor or m outside its range.
+ *      rv_grasp_quality_forward_train: d_logits [m] are rv_grasp_quality's logits of the same rows, bit for bit; the
+ *      workspace keeps per sample the pooled c1 and c2, which position of its 2 x 2 window each pool chose (v00, then
+ *      v01, v10, v11 each under a strict >: ties go to the first), f1, p, f2 and the normalised grasp depth.
+ *      rv_grasp_quality_backward: d_grad [weight_count] in the blob's layout, every float written, from d_dlogits [m] and
+ *      the workspace the forward entry filled for the SAME weights, images and depths.  Every gradient is a float32 chain
+ *      from +0 whose order depends on the shapes alone (no atomics, no dependence on grid, tile or m's divisibility):
+ *        relu passes where the stored activation is > 0; a pool window passes to its chosen position when the pooled
+ *        value is > 0; what is not passed is +0.
+ *        fc layers: the gradient at an input is the fma chain over the layer's outputs o ascending of (dy[o], W[o][i]);
+ *        dW[o][i] is the fma chain over the samples b ascending of (dy[b][o], x[b][i]), db[o] the sum chain of dy[b][o].
+ *        conv2 and conv1: per sample, s[co][ci][ky][kx] is the fma chain over the passing pool windows of channel co in
+ *        row-major order of (dz, the zero-padded input at the chosen position shifted by the tap), the bias part the sum
+ *        chain of dz over the same windows; dW and db are the sum chains of these over b ascending.  The gradient at c1
+ *        is the fma chain over (co, ky, kx) ascending of the taps that land on a chosen position of a passing window.
+ *        No gradient goes to the image or the grasp depth.
+ *      rv_adam_step, per element: m' = fma(beta1, m, (1 - beta1) g); v' = fma(beta2, v, ((1 - beta2) g) g);
+ *      w' = w - (lr (m' corr1)) / (sqrtf(v' corr2) + eps), every operation rounded on its own, sqrtf and / correctly;
+ *      corr1 = 1 / (1 - beta1^t) and corr2 = 1 / (1 - beta2^t) are the caller's (float64, rounded once).
+ *      All four are stateless like rv_grasp_quality: the world supplies the device and the stream, no env is read or
+ *      written; asynchronous on the world's stream.  RV_ERR_VALUE before any launch, with every output untouched: a NULL
+ *      pointer, a buffer that is not 4-byte aligned, a model rv_grasp_quality refuses, a normalisation constant that is
+ *      not finite, m outside [1, RV_GQ_MAX_BATCH], d_grad overlapping an input or the workspace, the workspace, the
+ *      logits and the weights overlapping one another, count < 1, Adam buffers that overlap, an Adam parameter that is
+ *      not finite, a beta outside [0, 1), a nonzero reserved word. ---- */
+#define RV_GQ_MAX_BATCH 4096
+int64_t rv_grasp_quality_train_workspace_floats(const rv_grasp_quality_model* h_model, int64_t m);
+int  rv_grasp_quality_forward_train(rv_world* w, const rv_grasp_quality_model* h_model, const float* d_weights,
+                                    const float* d_images, const float* d_grasp_depths, int64_t m,
+                                    float* d_workspace, float* d_logits);
+int  rv_grasp_quality_backward(rv_world* w, const rv_grasp_quality_model* h_model, const float* d_weights,
+                               const float* d_images, const float* d_grasp_depths, const float* d_dlogits, int64_t m,
+                               float* d_workspace, float* d_grad);
+typedef struct rv_adam_params { float lr, beta1, beta2, eps, corr1, corr2; int32_t reserved[2]; } rv_adam_params;
+int  rv_adam_step(rv_world* w, const rv_adam_params* h_params, int64_t count, float* d_w, const float* d_g,
+                  float* d_m, float* d_v);
 /* ---- cross-entropy refinement of grasp candidates: the step between two scorings (score, keep the elites, resample
  *      around them, score again -- how a grasp-quality network is normally used; with try_grasps rewards as scores, an
  *      evolutionary search with the simulator as the model).  One launch per iteration; the arithmetic, operation for

@@ -358,6 +358,28 @@ GRASP_QUALITY_API = {
 }
 
 
+RV_GQ_MAX_BATCH = 4096
+
+
+class rv_adam_params(C.Structure):
+    _fields_ = [
+        ('lr', C.c_float), ('beta1', C.c_float), ('beta2', C.c_float), ('eps', C.c_float), ('corr1', C.c_float),
+        ('corr2', C.c_float), ('reserved', i32 * 2),
+    ]
+
+
+# the training step of the grasp-quality network (include/rovat.h); lib.load() binds them from here
+GRASP_TRAIN_API = {
+    'rv_grasp_quality_train_workspace_floats': (C.c_int64, [C.POINTER(rv_grasp_quality_model), C.c_int64]),
+    'rv_grasp_quality_forward_train': (C.c_int, [C.c_void_p, C.POINTER(rv_grasp_quality_model), C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    'rv_grasp_quality_backward': (C.c_int, [C.c_void_p, C.POINTER(rv_grasp_quality_model), C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    'rv_adam_step': (C.c_int, [C.c_void_p, C.POINTER(rv_adam_params), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                               C.c_void_p]),
+}
+
+
 RV_GR_MAX_ITERATION = 1 << 26
 RV_GR_MAX_MACRO_INDEX = 1 << 24
 

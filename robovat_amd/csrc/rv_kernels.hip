@@ -14,6 +14,10 @@
 //                   image, the grasp row wave-uniform, a nearest-neighbour gather (rv_dev_grasp_sampler.h)
 //   k_grasp_quality the grasp-quality network: a workgroup per 8 crops, activations in LDS, conv2 / fc1 / fc2 on the
 //                   f32 MFMA, conv1 / pose / logit as FMA chains on the VALU (rv_dev_grasp_quality.h)
+//   k_gq_train_forward / k_gq_train_backward_sample / k_gq_train_backward_weights / k_adam_step   a training step of that
+//                   network: the forward pass keeping its activations, a workgroup per sample for the data gradients and
+//                   the convolutions' partial sums, a thread per weight for the chains over the batch, Adam per element
+//                   (rv_dev_grasp_train.h)
 //   k_*             small one-thread-per-env accessors behind the getters,
 //                   setters, observation, reward and policy entry points
 #include <hip/hip_runtime.h>
@@ -41,6 +45,7 @@
 #include "rv_dev_push_sampler.h"
 #include "rv_dev_push_route.h"
 #include "rv_dev_view.h"
+#include "rv_dev_grasp_train.h"
 
 using namespace rv;
 
@@ -1481,6 +1486,119 @@ int rv_grasp_quality(rv_world* w, const rv_grasp_quality_model* h_model, const f
   a.rows = (uint32_t)rows;
   const dim3 grid((unsigned)((rows + RV_GQ_BATCH - 1) / RV_GQ_BATCH));
   hipLaunchKernelGGL(k_grasp_quality, grid, dim3(RV_GQ_TPB), lds, w->stream, a, d_weights);
+  HIPCHK(hipGetLastError());
+  return RV_OK;
+}
+// -- a training step of the grasp-quality network (rv_dev_grasp_train.h)
+static bool gq_norm_finite(const rv_grasp_quality_model& m) {
+  const float big = 3.402823466e38f;
+  const auto finite = [big](float v) { return v >= -big && v <= big; };
+  return finite(m.im_mean) && finite(m.im_inv_std) && finite(m.z_mean) && finite(m.z_inv_std);
+}
+static bool ranges_overlap(const void* a, size_t abytes, const void* b, size_t bbytes) {
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  return a0 < b0 + bbytes && b0 < a0 + abytes;
+}
+static GtArgs gt_args(const rv_grasp_quality_model& m, int64_t rows) {
+  GtArgs a;
+  a.images = nullptr; a.depths = nullptr; a.dlogits = nullptr; a.ws = nullptr; a.logits = nullptr; a.grad = nullptr;
+  a.h = m.height; a.w = m.width; a.c1 = m.c1; a.c2 = m.c2; a.f1 = m.f1; a.f2 = m.f2; a.p = m.p;
+  a.im_mean = m.im_mean; a.im_inv_std = m.im_inv_std; a.z_mean = m.z_mean; a.z_inv_std = m.z_inv_std;
+  a.rows = (uint32_t)rows;
+  return a;
+}
+int64_t rv_grasp_quality_train_workspace_floats(const rv_grasp_quality_model* h_model, int64_t m) {
+  if (!h_model || !gq_model_ok(*h_model) || m < 1 || m > RV_GQ_MAX_BATCH) return -1;
+  const rv_grasp_quality_model& q = *h_model;
+  return m * (int64_t)gt_layout(q.height, q.width, q.c1, q.c2, q.f1, q.f2, q.p).stride;
+}
+int rv_grasp_quality_forward_train(rv_world* w, const rv_grasp_quality_model* h_model, const float* d_weights,
+                                   const float* d_images, const float* d_grasp_depths, int64_t m,
+                                   float* d_workspace, float* d_logits) {
+  WCHK(w);
+  if (!h_model) return fail(RV_ERR_VALUE, "rv_grasp_quality_forward_train: null model");
+  NEED(d_weights, "rv_grasp_quality_forward_train"); NEED(d_images, "rv_grasp_quality_forward_train");
+  NEED(d_grasp_depths, "rv_grasp_quality_forward_train"); NEED(d_workspace, "rv_grasp_quality_forward_train");
+  NEED(d_logits, "rv_grasp_quality_forward_train");
+  const rv_grasp_quality_model& q = *h_model;
+  if (!aligned_to(d_weights, 4) || !aligned_to(d_images, 4) || !aligned_to(d_grasp_depths, 4) || !aligned_to(d_workspace, 4) ||
+      !aligned_to(d_logits, 4))
+    return fail(RV_ERR_VALUE, "rv_grasp_quality_forward_train: the buffers must be 4-byte aligned");
+  if (!gq_model_ok(q)) return fail(RV_ERR_VALUE, "rv_grasp_quality_forward_train: a size of the model is outside its range");
+  if (!gq_norm_finite(q)) return fail(RV_ERR_VALUE, "rv_grasp_quality_forward_train: a normalisation constant is not finite");
+  if (m < 1 || m > RV_GQ_MAX_BATCH) return fail(RV_ERR_VALUE, "rv_grasp_quality_forward_train: m outside [1, RV_GQ_MAX_BATCH]");
+  const GqLayout L = gq_layout(q.height, q.width, q.c1, q.c2, q.f1, q.f2, q.p);
+  const GtLayout T = gt_layout(q.height, q.width, q.c1, q.c2, q.f1, q.f2, q.p);
+  const size_t wsb = (size_t)m * (size_t)T.stride * sizeof(float);
+  if (ranges_overlap(d_workspace, wsb, d_logits, (size_t)m * sizeof(float)) ||
+      ranges_overlap(d_workspace, wsb, d_weights, (size_t)L.count * sizeof(float)) ||
+      ranges_overlap(d_logits, (size_t)m * sizeof(float), d_weights, (size_t)L.count * sizeof(float)))
+    return fail(RV_ERR_VALUE, "rv_grasp_quality_forward_train: d_workspace, d_logits and d_weights must not overlap");
+  const size_t lds = (size_t)L.l_floats * sizeof(float);
+  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_gq_train_forward), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  GtArgs a = gt_args(q, m);
+  a.images = d_images; a.depths = d_grasp_depths; a.ws = d_workspace; a.logits = d_logits;
+  const dim3 grid((unsigned)((m + RV_GQ_BATCH - 1) / RV_GQ_BATCH));
+  hipLaunchKernelGGL(k_gq_train_forward, grid, dim3(RV_GQ_TPB), lds, w->stream, a, d_weights);
+  HIPCHK(hipGetLastError());
+  return RV_OK;
+}
+int rv_grasp_quality_backward(rv_world* w, const rv_grasp_quality_model* h_model, const float* d_weights,
+                              const float* d_images, const float* d_grasp_depths, const float* d_dlogits, int64_t m,
+                              float* d_workspace, float* d_grad) {
+  WCHK(w);
+  if (!h_model) return fail(RV_ERR_VALUE, "rv_grasp_quality_backward: null model");
+  NEED(d_weights, "rv_grasp_quality_backward"); NEED(d_images, "rv_grasp_quality_backward");
+  NEED(d_grasp_depths, "rv_grasp_quality_backward"); NEED(d_dlogits, "rv_grasp_quality_backward");
+  NEED(d_workspace, "rv_grasp_quality_backward"); NEED(d_grad, "rv_grasp_quality_backward");
+  const rv_grasp_quality_model& q = *h_model;
+  if (!aligned_to(d_weights, 4) || !aligned_to(d_images, 4) || !aligned_to(d_grasp_depths, 4) || !aligned_to(d_dlogits, 4) ||
+      !aligned_to(d_workspace, 4) || !aligned_to(d_grad, 4))
+    return fail(RV_ERR_VALUE, "rv_grasp_quality_backward: the buffers must be 4-byte aligned");
+  if (!gq_model_ok(q)) return fail(RV_ERR_VALUE, "rv_grasp_quality_backward: a size of the model is outside its range");
+  if (!gq_norm_finite(q)) return fail(RV_ERR_VALUE, "rv_grasp_quality_backward: a normalisation constant is not finite");
+  if (m < 1 || m > RV_GQ_MAX_BATCH) return fail(RV_ERR_VALUE, "rv_grasp_quality_backward: m outside [1, RV_GQ_MAX_BATCH]");
+  const GqLayout L = gq_layout(q.height, q.width, q.c1, q.c2, q.f1, q.f2, q.p);
+  const GtLayout T = gt_layout(q.height, q.width, q.c1, q.c2, q.f1, q.f2, q.p);
+  const size_t gb = (size_t)L.count * sizeof(float), mb = (size_t)m * sizeof(float);
+  if (ranges_overlap(d_grad, gb, d_weights, gb) || ranges_overlap(d_grad, gb, d_images, mb * (size_t)(q.height * q.width)) ||
+      ranges_overlap(d_grad, gb, d_grasp_depths, mb) || ranges_overlap(d_grad, gb, d_dlogits, mb) ||
+      ranges_overlap(d_grad, gb, d_workspace, mb * (size_t)T.stride))
+    return fail(RV_ERR_VALUE, "rv_grasp_quality_backward: d_grad must not overlap an input or the workspace");
+  const size_t lds = (size_t)T.l_floats * sizeof(float);
+  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_gq_train_backward_sample), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  GtArgs a = gt_args(q, m);
+  a.images = d_images; a.depths = d_grasp_depths; a.dlogits = d_dlogits; a.ws = d_workspace; a.grad = d_grad;
+  hipLaunchKernelGGL(k_gq_train_backward_sample, dim3((unsigned)m), dim3(RV_GT_TPB), lds, w->stream, a, d_weights);
+  HIPCHK(hipGetLastError());
+  const dim3 grid((unsigned)((L.count + RV_GT_TPB - 1) / RV_GT_TPB));
+  hipLaunchKernelGGL(k_gq_train_backward_weights, grid, dim3(RV_GT_TPB), 0, w->stream, a);
+  HIPCHK(hipGetLastError());
+  return RV_OK;
+}
+int rv_adam_step(rv_world* w, const rv_adam_params* h_params, int64_t count, float* d_w, const float* d_g, float* d_m, float* d_v) {
+  WCHK(w);
+  if (!h_params) return fail(RV_ERR_VALUE, "rv_adam_step: null params");
+  NEED(d_w, "rv_adam_step"); NEED(d_g, "rv_adam_step"); NEED(d_m, "rv_adam_step"); NEED(d_v, "rv_adam_step");
+  if (!aligned_to(d_w, 4) || !aligned_to(d_g, 4) || !aligned_to(d_m, 4) || !aligned_to(d_v, 4))
+    return fail(RV_ERR_VALUE, "rv_adam_step: the buffers must be 4-byte aligned");
+  if (count < 1 || count > ((int64_t)0x7fffffff) * RV_GT_TPB) return fail(RV_ERR_VALUE, "rv_adam_step: count < 1 or too large for one launch");
+  const rv_adam_params& p = *h_params;
+  const float big = 3.402823466e38f;
+  const auto finite = [big](float v) { return v >= -big && v <= big; };
+  if (!finite(p.lr) || !finite(p.beta1) || !finite(p.beta2) || !finite(p.eps) || !finite(p.corr1) || !finite(p.corr2))
+    return fail(RV_ERR_VALUE, "rv_adam_step: a parameter is not finite");
+  if (!(p.beta1 >= 0.0f && p.beta1 < 1.0f) || !(p.beta2 >= 0.0f && p.beta2 < 1.0f))
+    return fail(RV_ERR_VALUE, "rv_adam_step: beta1 or beta2 outside [0, 1)");
+  if (p.reserved[0] != 0 || p.reserved[1] != 0) return fail(RV_ERR_VALUE, "rv_adam_step: a reserved word is not 0");
+  const size_t bytes = (size_t)count * sizeof(float);
+  if (ranges_overlap(d_w, bytes, d_g, bytes) || ranges_overlap(d_w, bytes, d_m, bytes) || ranges_overlap(d_w, bytes, d_v, bytes) ||
+      ranges_overlap(d_g, bytes, d_m, bytes) || ranges_overlap(d_g, bytes, d_v, bytes) || ranges_overlap(d_m, bytes, d_v, bytes))
+    return fail(RV_ERR_VALUE, "rv_adam_step: the four buffers must not overlap");
+  GtAdam a;
+  a.lr = p.lr; a.beta1 = p.beta1; a.beta2 = p.beta2; a.eps = p.eps; a.corr1 = p.corr1; a.corr2 = p.corr2;
+  const dim3 grid((unsigned)((count + RV_GT_TPB - 1) / RV_GT_TPB));
+  hipLaunchKernelGGL(k_adam_step, grid, dim3(RV_GT_TPB), 0, w->stream, a, (size_t)count, d_w, d_g, d_m, d_v);
   HIPCHK(hipGetLastError());
   return RV_OK;
 }

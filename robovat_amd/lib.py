@@ -41,6 +41,7 @@ SYMBOLS = [
     'rv_get_route_field', 'rv_policy_route_multi', 'rv_plan_propose_route',
     'rv_grasp_crops',
     'rv_grasp_quality_weight_count', 'rv_grasp_quality',
+    'rv_grasp_quality_train_workspace_floats', 'rv_grasp_quality_forward_train', 'rv_grasp_quality_backward', 'rv_adam_step',
     'rv_grasp_refine',
     'rv_render_view',
 ]
@@ -187,7 +188,7 @@ def load():
         getattr(lib, name).argtypes = [vp, vp]
     abi.bind_state_api(lib)
     for api in (abi.ANTIPODAL_API, abi.CEM_API, abi.DEPTH_NOISE_API, abi.PUSH_PROPOSAL_API, abi.PUSH_ROUTE_API,
-                abi.GRASP_CROP_API, abi.GRASP_QUALITY_API, abi.GRASP_REFINE_API, abi.VIEW_API):
+                abi.GRASP_CROP_API, abi.GRASP_QUALITY_API, abi.GRASP_TRAIN_API, abi.GRASP_REFINE_API, abi.VIEW_API):
         for name, (res, args) in api.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, list(args)
@@ -320,6 +321,20 @@ def grasp_refine_params(n_elites=1, sigma_center=3.0, sigma_angle=0.15, sigma_de
                                    seed=int(seed) & 0xFFFFFFFF, n_elites=int(n_elites), sigma_center=float(sigma_center),
                                    sigma_angle=float(sigma_angle), sigma_depth=float(sigma_depth))
     return _override(p, 'grasp_refine_params', overrides)
+
+
+def adam_params(step, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
+    """An ``rv_adam_params`` for update number ``step`` (t >= 1): lr, the betas and eps rounded to float32, and the bias
+    corrections 1 / (1 - beta^t) computed in float64 from the float32 betas and rounded once."""
+    import numpy as np
+    step = int(step)
+    if step < 1:
+        raise ValueError('adam_params: step must be >= 1, got %d' % step)
+    b1, b2 = float(np.float32(betas[0])), float(np.float32(betas[1]))
+    if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
+        raise ValueError('adam_params: betas outside [0, 1): %r' % (betas,))
+    return abi.rv_adam_params(lr=float(lr), beta1=b1, beta2=b2, eps=float(eps), corr1=1.0 / (1.0 - b1 ** step),
+                              corr2=1.0 / (1.0 - b2 ** step))
 
 
 def view_params(n_views, height, width, supersample=1):
@@ -771,6 +786,83 @@ class World(object):
         desc = model.descriptor()
         check(self.lib.rv_grasp_quality(self.h, C.byref(desc), self._ptr(blob), self._ptr(x), self._ptr(z), k, self._ptr(out)))
         return out
+
+    # -- a training step of the grasp-quality network (include/rovat.h: rv_grasp_quality_forward_train, _backward, rv_adam_step)
+    def _train_batch(self, who, model, images, grasp_depths):
+        torch = self.torch
+        h, w = int(model.sizes['height']), int(model.sizes['width'])
+        x = torch.as_tensor(images, dtype=torch.float32, device=self.device)
+        if x.dim() != 3 or tuple(x.shape[1:]) != (h, w) or not 1 <= int(x.shape[0]) <= abi.RV_GQ_MAX_BATCH:
+            raise ValueError('%s: images must be [m, %d, %d] with m in [1, %d], got %s' % (who, h, w, abi.RV_GQ_MAX_BATCH, tuple(x.shape)))
+        m = int(x.shape[0])
+        z = torch.as_tensor(grasp_depths, dtype=torch.float32, device=self.device)
+        if tuple(z.shape) != (m,):
+            raise ValueError('%s: grasp_depths must be [m] = [%d], got %s' % (who, m, tuple(z.shape)))
+        return x.contiguous(), z.contiguous(), m
+
+    def _train_buffer(self, who, name, t, count, at_least=False):
+        torch = self.torch
+        if not (torch.is_tensor(t) and t.dtype == torch.float32 and t.device == self.device and t.dim() == 1 and t.is_contiguous()
+                and (int(t.numel()) >= count if at_least else int(t.numel()) == count)):
+            raise ValueError('%s: %s must be a contiguous float32 tensor of %s%d floats on %s'
+                             % (who, name, 'at least ' if at_least else '', count, self.device))
+        return t
+
+    def grasp_quality_train_workspace(self, model, m):
+        """a new workspace tensor for ``m`` samples of ``model`` (rv_grasp_quality_train_workspace_floats)"""
+        desc = model.descriptor()
+        floats = int(self.lib.rv_grasp_quality_train_workspace_floats(C.byref(desc), int(m)))
+        if floats < 0:
+            raise ValueError('grasp_quality_train_workspace: the model or m = %d is refused' % (int(m),))
+        return self._new((floats,), self.torch.float32)
+
+    def grasp_quality_forward_train(self, model, weights, images, grasp_depths, workspace=None, out=None):
+        """rv_grasp_quality_forward_train: the logits [m] of ``images`` [m, h, w] and ``grasp_depths`` [m] under the device
+        blob ``weights`` (float32 [model.weight_count()], the layout of ``model.blob()``; ``model`` supplies the sizes and
+        the normalisation only), bit for bit ``grasp_quality``'s, and the activations the backward pass reads in
+        ``workspace`` (None: a new one).  Returns (logits, workspace).  Asynchronous."""
+        who = 'grasp_quality_forward_train'
+        x, z, m = self._train_batch(who, model, images, grasp_depths)
+        desc = model.descriptor()
+        wt = self._train_buffer(who, 'weights', weights, model.weight_count())
+        need = int(self.lib.rv_grasp_quality_train_workspace_floats(C.byref(desc), m))
+        if need < 0:
+            raise ValueError('%s: the model is refused' % who)
+        ws = self.grasp_quality_train_workspace(model, m) if workspace is None else self._train_buffer(who, 'workspace', workspace, need, True)
+        out = self._new((m,), self.torch.float32) if out is None else self._train_buffer(who, 'out', out, m)
+        check(self.lib.rv_grasp_quality_forward_train(self.h, C.byref(desc), self._ptr(wt), self._ptr(x), self._ptr(z), m,
+                                                      self._ptr(ws), self._ptr(out)))
+        return out, ws
+
+    def grasp_quality_backward(self, model, weights, images, grasp_depths, dlogits, workspace, out=None):
+        """rv_grasp_quality_backward: the gradient [model.weight_count()], in the blob's layout, of a loss whose derivative
+        with respect to logit b is ``dlogits[b]``; ``workspace`` as ``grasp_quality_forward_train`` left it for the same
+        weights, images and depths.  Deterministic: every entry is a float32 chain in a fixed order
+        (csrc/rv_dev_grasp_train.h).  Asynchronous."""
+        who = 'grasp_quality_backward'
+        x, z, m = self._train_batch(who, model, images, grasp_depths)
+        desc = model.descriptor()
+        count = model.weight_count()
+        wt = self._train_buffer(who, 'weights', weights, count)
+        g = self._train_buffer(who, 'dlogits', dlogits, m)
+        need = int(self.lib.rv_grasp_quality_train_workspace_floats(C.byref(desc), m))
+        if need < 0:
+            raise ValueError('%s: the model is refused' % who)
+        ws = self._train_buffer(who, 'workspace', workspace, need, True)
+        out = self._new((count,), self.torch.float32) if out is None else self._train_buffer(who, 'out', out, count)
+        check(self.lib.rv_grasp_quality_backward(self.h, C.byref(desc), self._ptr(wt), self._ptr(x), self._ptr(z), self._ptr(g), m,
+                                                 self._ptr(ws), self._ptr(out)))
+        return out
+
+    def adam_step(self, weights, grad, m, v, step, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
+        """rv_adam_step: one Adam update of ``weights`` in place from ``grad``, with the moments ``m`` and ``v`` (all float32
+        [count] device tensors); ``step`` is t >= 1, the bias corrections 1 / (1 - beta^t) are computed here in float64."""
+        count = int(weights.numel()) if self.torch.is_tensor(weights) else -1
+        for name, t in (('weights', weights), ('grad', grad), ('m', m), ('v', v)):
+            self._train_buffer('adam_step', name, t, count)
+        check(self.lib.rv_adam_step(self.h, C.byref(adam_params(step, lr, betas, eps)), count, self._ptr(weights), self._ptr(grad),
+                                    self._ptr(m), self._ptr(v)))
+        return weights
 
     # -- cross-entropy refinement of grasp candidates (include/rovat.h: rv_grasp_refine)
     def grasp_refine(self, depth, grasps, scores, params, sampler_params, count=None, status=None, actions4=False):

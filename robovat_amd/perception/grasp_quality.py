@@ -115,6 +115,31 @@ class GraspQualityModel(object):
         assert out.size == self.weight_count()
         return out
 
+    @classmethod
+    def from_blob(cls, blob, norm=None, **sizes):
+        """The inverse of ``blob()``: the model of these sizes whose ``blob()`` is ``blob``, bit for bit."""
+        full = dict(DEFAULT_SIZES)
+        for k, v in sizes.items():
+            if k not in SIZE_NAMES:
+                raise TypeError('GraspQualityModel: unknown size %r' % (k,))
+            full[k] = int(v)
+        check_sizes(full)
+        shapes = param_shapes(**full)
+        flat = np.ascontiguousarray(np.asarray(blob, np.float32)).ravel()
+        if flat.size != sum(int(np.prod(s)) for s in shapes.values()):
+            raise ValueError('GraspQualityModel.from_blob: %d floats, these sizes have %d'
+                             % (flat.size, sum(int(np.prod(s)) for s in shapes.values())))
+        params, at = {}, 0
+        for name in PARAM_NAMES:
+            shape = shapes[name]
+            n = int(np.prod(shape))
+            part = flat[at:at + n]
+            at += n
+            if name in ('conv2.weight', 'fc1.weight', 'fc2.weight'):      # K-major in the blob: [inputs][outputs]
+                part = part.reshape(n // shape[0], shape[0]).T
+            params[name] = np.ascontiguousarray(part).reshape(shape).copy()
+        return cls(params, norm, **full)
+
     def save(self, path):
         """one ``.npz``: the sizes, the normalisation constants and every parameter under its name"""
         data = {'sizes': np.array([self.sizes[k] for k in SIZE_NAMES], np.int32),

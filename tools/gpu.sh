@@ -34,6 +34,9 @@
 #                  duration from a profiler run of the kernel half, and its resources
 #   grasp_refine   tools/grasp_refine_bench.py: rv_grasp_refine against a torch restatement of the step and next to one
 #                  scoring, and the success rate of CEMGraspPolicy next to the other grasp policies; the kernel's resources
+#   grasp_train    tools/grasp_train_bench.py: a training step of the grasp-quality network against torch eager, six epochs
+#                  with backend='hip', and the retraining experiment on refined candidates; then the kernels' own
+#                  durations from a profiler run of the step half, and their resources
 #   render_view    tools/render_view_bench.py: rv_render_view next to rv_render_rgb, supersampling in rays per second, and
 #                  record_step next to a plain step(); the kernel's resources
 #   lanes          SQ_THREAD_CYCLES_VALU / SQ_ACTIVE_INST_VALU lane-utilisation pass (headline and no-deactivation)
@@ -117,6 +120,14 @@ for STAGE in "$@"; do
       python tools/kernel_resources.py > $O/kernel_resources_all.txt 2>&1
       grep -h "^kernel\|grasp_refine" $O/kernel_resources_all.txt > $O/grasp_refine_kernel_resources.txt
       tail -30 $O/grasp_refine_bench.txt; cat $O/grasp_refine_kernel_resources.txt ;;
+    grasp_train)
+      timeout -k 10 1100 python tools/grasp_train_bench.py --out $O/grasp_train_bench.txt > $O/grasp_train_bench.log 2>&1 &&
+        timeout -k 10 300 rocprofv3 --kernel-trace --stats -d /tmp/rv_grasp_train_prof_$TAG -o gt --output-format csv -- python tools/grasp_train_bench.py --skip-experiment --iters 10 --warmup 2 > $O/grasp_train_prof.log 2>&1
+      echo "grasp_train rc=$?" >> $O/time.txt
+      grep -h "Name\|gq_train\|adam_step" $(find /tmp/rv_grasp_train_prof_$TAG -name '*kernel_stats.csv') > $O/grasp_train_kernel_stats.txt      # (the trace itself is too large to keep)
+      python tools/kernel_resources.py > $O/kernel_resources_all.txt 2>&1
+      grep -h "^kernel\|gq_train\|adam_step\|k_grasp_quality" $O/kernel_resources_all.txt > $O/grasp_train_kernel_resources.txt
+      tail -60 $O/grasp_train_bench.txt; cat $O/grasp_train_kernel_stats.txt $O/grasp_train_kernel_resources.txt ;;
     render_view)
       timeout -k 10 900 python tools/render_view_bench.py --out $O/render_view_bench.txt > $O/render_view_bench.log 2>&1
       echo "render_view rc=$?" >> $O/time.txt
