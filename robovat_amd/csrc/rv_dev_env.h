@@ -488,6 +488,9 @@ RV_DEV void point_world(const Shared& S, const Consts& K, int kind, int a, int b
   else if (kind == 1) *wb = to_world_body(S, b, p.lb);
   else *wb = to_world_frame(S, K.arm->col_frame[p.col], p.lb);
 }
+// (the refresh lanes of sim_substep_heavy hold a device copy of this function, brk_of and point_world written on operands
+// loaded up front -- DESIGN.md §10, "LDS staging": a change here is made there too; tests/test_gpu_np_prep.py and the parity
+// sweep compare it with the oracle)
 // refresh of ONE cached point: its current distance, and whether it broke (too far apart
 // along the normal, or the two anchors drifted apart tangentially)
 RV_DEV void refresh_point(const Shared& S, const Consts& K, int kind, int a, int b, const DevMan& m, int i, float* dist, int* rm) {
@@ -678,6 +681,8 @@ struct OwnerInfo {
   int n_outer, n_inner;
   v3 guess0;
 };
+// (the host emulation runs this text; on the device the owner lanes of sim_substep_heavy run its twin owner_decode_masks
+// below: a change to an arm here is made there too)
 RV_DEV void owner_decode(const Shared& S, const Consts& K, int owner, int arm_on, OwnerInfo& o) {
   const rv_config* c = K.cfg; const DevEnv& e = S.e;
   v3 tc = mk(c->table_center[0], c->table_center[1], e.table_z - 0.5f * c->table_thickness);
@@ -727,6 +732,76 @@ RV_DEV void owner_decode(const Shared& S, const Consts& K, int owner, int arm_on
     }
   }
 }
+
+#if RV_ON_DEVICE
+// owner_decode for the owner lanes of sim_substep_heavy: the predicates of its four arms are bits of the flag masks
+// taken at the top of the heavy part (bit b: body b present / asleep / static), and everything an arm reads is loaded
+// ahead of all four through clamped indices ("LDS staging").  The arithmetic is owner_decode's on the
+// locals.
+RV_DEV void owner_decode_masks(const Shared& S, const Consts& K, const int owner, const int arm_on,
+                               const unsigned present_m, const unsigned asleep_m, const unsigned static_m, OwnerInfo& o) {
+  const rv_config* c = K.cfg; const DevEnv& e = S.e;
+  const int cls = owner < RV_MAXB ? 0 : (owner < RV_MAXB + RV_NBB ? 1 : (owner < RV_NMAN ? 2 : 3));
+  const int kp = cls == 1 ? owner - RV_MAXB : 0;
+  const int a = cls == 0 ? owner : (cls == 1 ? bb_a(kp) : (cls == 2 ? owner - RV_MAXB - RV_NBB : 0));
+  const int b = cls == 1 ? bb_b(kp) : 0;
+  const int col = cls == 3 && owner < RV_NMAN + RV_NCOL ? owner - RV_NMAN : 0;
+  // ---- loads
+  const float tcx = c->table_center[0], tcy = c->table_center[1], thx = c->table_half[0], thy = c->table_half[1];
+  const float tthick = c->table_thickness, margin = c->margin, breaking = c->breaking, cqd = c->contact_query_dist, ground_z = c->ground_z;
+  const float table_z = e.table_z;
+  const float rad_a = e.radius[a], rad_b = e.radius[b];
+  const v3 pos_a = ld3(e.body[a]), pos_b = ld3(e.body[b]);
+  const int nh_a = S.n_hulls[a], nh_b = S.n_hulls[b];
+  const float colr = S.s.colr[col], minz = S.s.colmin[col][2];
+  const v3 colc = ld3(S.s.colc[col]), hh = ld3(K.arm->col_half[col]);
+  // ---- the arms
+  const v3 tc = mk(tcx, tcy, table_z - 0.5f * tthick);
+  const v3 th = mk(thx, thy, 0.5f * tthick);
+  const unsigned pr_a = (present_m >> a) & 1u, pr_b = (present_m >> b) & 1u, sl_a = (asleep_m >> a) & 1u, sl_b = (asleep_m >> b) & 1u;
+  const unsigned st_a = (static_m >> a) & 1u, st_b = (static_m >> b) & 1u;
+  o.role = -1; o.kind = 0; o.a = 0; o.b = -1; o.mi = 0; o.clear = 0; o.live = 0; o.n_outer = 0; o.n_inner = 0;
+  o.guess0 = mk(0.0f, 0.0f, 1.0f);
+  if (cls == 0) {
+    o.a = a; o.mi = RV_TIDX(a); o.kind = 0;
+    if (!pr_a || st_a) o.clear = 1;      // (a static body: pair manifolds only)
+    else if (!sl_a) {
+      o.live = 1;
+      float r = rad_a + breaking * (rad_a - margin);
+      if (pos_a.z + rad_a < table_z - tthick) {
+        if (!(pos_a.z - ground_z >= r)) { o.role = 0; o.n_outer = 1; o.n_inner = nh_a; }
+      } else if (!(sphere_box_dist2(pos_a, tc, th) >= r * r)) {
+        o.role = 0; o.n_outer = 1; o.n_inner = nh_a;
+        o.guess0 = mk(0.0f, 0.0f, pos_a.z - tc.z);
+      }
+    }
+  } else if (cls == 1) {
+    o.a = a; o.b = b; o.mi = RV_BBIDX(kp); o.kind = 1;
+    if (!(pr_a && pr_b) || (st_a && st_b)) o.clear = 1;
+    else if (!sl_a && !sl_b) {
+      o.live = 1;
+      v3 d = sub(pos_a, pos_b);
+      float r = rad_a + rad_b + fminr(breaking * (rad_a - margin), breaking * (rad_b - margin));
+      if (!(dot(d, d) >= r * r)) { o.role = 1; o.n_outer = nh_a; o.n_inner = nh_b; o.guess0 = d; }
+    }
+  } else if (cls == 2) {
+    o.a = a; o.mi = RV_AIDX(a); o.kind = 2;
+    if (!pr_a || st_a) o.clear = 1;
+    else if (!sl_a) {
+      if (!arm_on) o.clear = 1;
+      else { o.live = 1; o.role = 2; o.n_outer = RV_NCOL; o.n_inner = nh_a; }
+    }
+  } else {
+    o.a = col;
+    if (arm_on) {
+      float r = colr + breaking * fsqrtr(hh.x * hh.x + hh.y * hh.y + hh.z * hh.z);
+      // rejection: the flag needs dist < query_dist and dist >= minz - table_z - margin
+      if (!(minz - table_z - margin >= cqd) &&
+          sphere_box_dist2(colc, tc, th) < r * r) { o.role = 3; o.n_outer = 1; o.n_inner = 1; }
+    }
+  }
+}
+#endif
 
 // Item k of an owner that runs queries (sim_substep_heavy): its k-th convex pair in pair order -- for an arm-body owner
 // the pairs of the collider boxes near the body only (S.s.cn) -- with everything the query and the apply part need of it.
@@ -3504,6 +3579,81 @@ RV_DEV void sim_substep_heavy(Shared& S, const Consts& K) {
   //      -- the state of a manifold after each pair is what one group working through the owner gives.
   //      All lanes of a group execute the same scalar program redundantly -- except inside support_v(),
   //      where each lane holds one hull vertex and a DPP all-reduce picks the extreme one.
+#if RV_ON_DEVICE
+  // The body flags of this substep, read ONCE: every lane loads the four flag words of body (lane & 3), loads first and no
+  // short circuit, and ballots taken by the whole wave turn them into wave-uniform masks in SGPRs (bit b: body b).  The
+  // phases of the preparation test bits of these instead of calling body_present / body_on / body_static, whose `&&`
+  // chains are one exposed LDS round trip and one exec-mask nest per word.  No flag changes between here and the
+  // integrate phase.
+  unsigned present_m, asleep_m, static_m, on_m;
+  {
+    const int lane = (int)threadIdx.x;
+    const DevEnv& e = S.e;
+    const int bl = lane & 3;
+    const int l_act = e.active[bl], l_frz = e.frozen[bl], l_slp = e.asleep[bl];
+    const float l_im = e.inv_mass[bl];
+    present_m = (unsigned)__builtin_amdgcn_ballot_w64((l_act != 0) & (l_frz == 0)) & 15u;
+    asleep_m = (unsigned)__builtin_amdgcn_ballot_w64(l_slp != 0) & 15u;
+    static_m = (unsigned)__builtin_amdgcn_ballot_w64(l_im == 0.0f) & 15u;
+    on_m = present_m & ~asleep_m;
+  }
+  const int arm_on_u = RV_UNI(arm_on);
+  // (0) one path for the three manifold kinds (loads first, stores last: DESIGN.md §10, "LDS staging"): the point, the
+  // breaking distance and the operands of both frames are loaded up front, those of the second frame -- body b of a pair
+  // manifold, the link frame of the point's collider box of an arm manifold, nothing for the table -- through clamped
+  // indices.  The arithmetic is refresh_point's on the locals: to_world_body and to_world_frame are the one expression
+  // add(pos, mulv(R, l)) on different operands.
+  RV_LANES_BEGIN
+    const DevEnv& e = S.e;
+    const int ln = lane < RV_NMAN * 4 ? lane : RV_NMAN * 4 - 1;
+    const int mi = ln >> 2, i = ln & 3;
+    const int kind = mi < RV_MAXB ? 0 : (mi < RV_MAXB + RV_NBB ? 1 : 2);
+    const int kp = kind == 1 ? mi - RV_MAXB : 0;
+    const int a = kind == 0 ? mi : (kind == 1 ? bb_a(kp) : mi - RV_MAXB - RV_NBB);
+    const int b = kind == 1 ? bb_b(kp) : 0;
+    const DevMan& m = e.man[mi];
+    const int n = m.n;
+    const v3 la = ld3(m.la[i]), lb = ld3(m.lb[i]), nrm = ld3(m.nrm[i]);
+    const int col_ = m.col[i], col = (unsigned)col_ < (unsigned)RV_NCOL ? col_ : 0;
+    const float breaking = c->breaking, margin = c->margin, rad_a = e.radius[a], rad_b = e.radius[b];
+    const v3 pos_a = ld3(e.body[a]);
+    float rot_a[9], rot_2[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) rot_a[k] = S.s.rot[a][k];
+    const int any_on_l = S.s.any_on, awake_l = e.awake_last;
+    const int f_ = arm->col_frame[col], f = (unsigned)f_ < (unsigned)RV_NFRAME ? f_ : 0;
+    const v3 hh = ld3(arm->col_half[col]);
+    const float* r2 = kind == 2 ? S.s.frot[f] : S.s.rot[b];
+    const float* p2 = kind == 2 ? e.fpos[f] : e.body[b];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) rot_2[k] = r2[k];
+    const v3 pos_2 = ld3(p2);
+    // whose manifold, and is it refreshed?  (the same conditions as owner_decode's `live`)
+    const unsigned on_a = (on_m >> a) & 1u, on_b = (on_m >> b) & 1u, st_a = (static_m >> a) & 1u, st_b = (static_m >> b) & 1u;
+    const int live = kind == 1 ? (int)(on_a & on_b & (1u ^ (st_a & st_b))) : (int)(on_a & (1u ^ st_a)) & (kind == 0 || arm_on);
+    // (brk_of: the square root of brk_col once per lane)
+    const float brk_a = breaking * (rad_a - margin);
+    const float brk_2 = kind == 1 ? breaking * (rad_b - margin) : breaking * fsqrtr(hh.x * hh.x + hh.y * hh.y + hh.z * hh.z);
+    const float brk = kind == 0 ? brk_a : fminr(brk_a, brk_2);
+    const v3 wa = add(pos_a, mulv(rot_a, la));
+    const v3 wb = kind == 0 ? lb : add(pos_2, mulv(rot_2, lb));
+    float d = dot(sub(wa, wb), nrm);
+    int rm = 0;
+    if (d > brk) rm = 1;
+    else {
+      v3 proj = madd(wa, nrm, -d);
+      v3 dr = sub(wb, proj);
+      if (dot(dr, dr) > brk * brk) rm = 1;
+    }
+    if (!(live && i < n)) { d = 0.0f; rm = 0; }
+    if (lane < RV_NMAN * 4) { S.s.rf_dist[lane] = d; S.s.rf_rm[lane] = rm; }
+#ifdef RV_DIAG_AWAKE_BODIES   // diagnostic build (tools/diag_lockstep.py): count awake BODIES per substep
+    if (lane == 59) S.e.awake_last = awake_l + __builtin_popcount(on_m) * 65536 + any_on_l;
+#else
+    if (lane == 59) S.e.awake_last = awake_l + any_on_l;
+#endif
+  RV_LANES_END
+#else
   RV_LANES_BEGIN
     const DevEnv& e = S.e;
     if (lane < RV_NMAN * 4) {
@@ -3526,13 +3676,41 @@ RV_DEV void sim_substep_heavy(Shared& S, const Consts& K) {
     if (lane == 59) S.e.awake_last += S.s.any_on;
 #endif
   RV_LANES_END
+#endif
+#if RV_ON_DEVICE
+  unsigned long long k0, k1;     // (body, box) proximity: the flags of body b sit on the five bits from RV_NMAN + RV_NCOL + 5 b
+  unsigned wv_m, at_m;           // bit b: body b has hulls in a convex query of this substep; bit col: S.s.atflag[col] (none: arm off)
+#endif
   RV_LANES_BEGIN
     DevEnv& e = S.e;
     int n_all = 0, near0 = 0, near1 = 0;      // this owner's convex pairs; (body, box) proximity flags of this lane
+#if RV_ON_DEVICE
+    // (body, box) proximity for the arm-body owners, two pairs per lane and both in straight-line code: the operands of
+    // both are loaded here, ahead of the owner lanes' stores (pair index clamped: every lane loads, the proximity lanes keep)
+    static_assert(RV_NCOL % 2 == 0, "the two pairs of a proximity lane belong to one body");
+    const int px_lane = lane >= RV_NMAN + RV_NCOL && lane < RV_NMAN + RV_NCOL + RV_MAXB * RV_NCOL / 2;
+    const int px_t = px_lane ? (lane - RV_NMAN - RV_NCOL) * 2 : 0;
+    const int px_b = px_t / RV_NCOL, px_col = px_t - px_b * RV_NCOL;
+    const float px_rad = e.radius[px_b], px_breaking = c->breaking, px_margin = c->margin;
+    const v3 px_pos = ld3(e.body[px_b]);
+    float px_lo[2][3], px_hi[2][3]; v3 px_hh[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+#pragma unroll
+      for (int x = 0; x < 3; ++x) { px_lo[t][x] = S.s.colmin[px_col + t][x]; px_hi[t][x] = S.s.colmax[px_col + t][x]; }
+      px_hh[t] = ld3(arm->col_half[px_col + t]);
+    }
+    const int at_l = S.s.atflag[lane >= RV_NMAN && lane < RV_NMAN + RV_NCOL ? lane - RV_NMAN : 0];
+    int wv_need = 0;
+#endif
     if (lane < RV_NMAN + RV_NCOL) {
       const int owner = lane;
       OwnerInfo o;
+#if RV_ON_DEVICE
+      owner_decode_masks(S, K, owner, arm_on, present_m, asleep_m, static_m, o);
+#else
       owner_decode(S, K, owner, arm_on, o);
+#endif
       int n_pairs = o.n_outer * o.n_inner;
       // (loads first, stores last: DESIGN.md §10, "LDS staging".  o.a is a collider box for the arm-table detectors, which
       // are never live: the index is clamped)
@@ -3569,8 +3747,25 @@ RV_DEV void sim_substep_heavy(Shared& S, const Consts& K) {
       S.s.ow_run[owner] = n_pairs;
 #endif
       n_all = n_pairs;
+#if RV_ON_DEVICE
+      wv_need = n_pairs > 0 && o.role >= 0 && o.role <= 2;
+#else
       if (n_pairs > 0 && o.role >= 0 && o.role <= 2) { S.s.wvneed[o.a] = 1; if (o.b >= 0) S.s.wvneed[o.b] = 1; }
+#endif
     }
+#if RV_ON_DEVICE
+    {
+      const int px_ok = arm_on && ((on_m & ~static_m) >> px_b & 1u);
+      const float brk_b = px_breaking * (px_rad - px_margin);
+      int nr[2];
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        const float r = px_rad + fminr(brk_b, px_breaking * fsqrtr(px_hh[t].x * px_hh[t].x + px_hh[t].y * px_hh[t].y + px_hh[t].z * px_hh[t].z));
+        nr[t] = px_ok && !(sphere_aabb_dist2(px_pos, px_lo[t], px_hi[t]) >= r * r);
+      }
+      if (px_lane) { S.s.cn[px_b][px_col] = nr[0]; S.s.cn[px_b][px_col + 1] = nr[1]; near0 = nr[0]; near1 = nr[1]; }
+    }
+#else
     if (lane >= RV_NMAN + RV_NCOL && lane < RV_NMAN + RV_NCOL + RV_MAXB * RV_NCOL / 2) {
       // (body, box) proximity for the arm-body owners, two pairs per lane
       for (int t = (lane - RV_NMAN - RV_NCOL) * 2; t < (lane - RV_NMAN - RV_NCOL) * 2 + 2; ++t) {
@@ -3584,13 +3779,24 @@ RV_DEV void sim_substep_heavy(Shared& S, const Consts& K) {
         if (t & 1) near1 = near; else near0 = near;
       }
     }
+#endif
 #if RV_ON_DEVICE
     {
       // (every ballot here is taken by all 64 lanes: the lanes without an owner / a proximity pair hold zeros)
       // an arm-body owner runs the pairs of the boxes near its body only: the flags of body b sit on the five lanes
       // from RV_NMAN + RV_NCOL + 5 b, even boxes in near0, odd ones in near1
       static_assert(RV_NCOL == 10, "five proximity lanes per body");
-      const unsigned long long k0 = __builtin_amdgcn_ballot_w64(near0 != 0), k1 = __builtin_amdgcn_ballot_w64(near1 != 0);
+      k0 = __builtin_amdgcn_ballot_w64(near0 != 0); k1 = __builtin_amdgcn_ballot_w64(near1 != 0);
+      // which bodies have hulls in a query (owners T(b) on lanes 0 .. 3, A(b) on 10 .. 13, the pairs (0,1) (0,2) (0,3) (1,2)
+      // (1,3) (2,3) on 4 .. 9), and the arm-table gate of the ten boxes (lanes 14 .. 23): masks in SGPRs for the vertex phase
+      static_assert(RV_MAXB == 4, "the pair owners' bodies as bit patterns");
+      {
+        const unsigned nm = (unsigned)__builtin_amdgcn_ballot_w64(wv_need != 0);
+        const unsigned bbm = (nm >> RV_MAXB) & 63u;
+        wv_m = (nm | (nm >> (RV_MAXB + RV_NBB))) & 15u;
+        wv_m |= ((bbm & 7u) ? 1u : 0u) | ((bbm & 25u) ? 2u : 0u) | ((bbm & 42u) ? 4u : 0u) | ((bbm & 52u) ? 8u : 0u);
+        at_m = arm_on_u ? ((unsigned)(__builtin_amdgcn_ballot_w64(at_l != 0) >> RV_NMAN) & ((1u << RV_NCOL) - 1u)) : 0u;
+      }
       int cnt = n_all;
       if (lane >= RV_MAXB + RV_NBB && lane < RV_NMAN) {
         const int sh = RV_NMAN + RV_NCOL + 5 * (lane - RV_MAXB - RV_NBB);
@@ -3635,6 +3841,32 @@ RV_DEV void sim_substep_heavy(Shared& S, const Consts& K) {
   RV_LANES_END
 #endif
   // world hull vertices of the bodies, and vertices of the collider boxes, that take part in a convex query
+#if RV_ON_DEVICE
+  // (what is needed comes from the masks of the owner phase, not from per-lane reads of wvneed, atflag and cn: a box is
+  // needed when its arm-table gate is open or some body is near it -- bit RV_NMAN + RV_NCOL + 5 b + col / 2 of k0 (even
+  // boxes) or k1 (odd ones), b = 0 .. 3)
+  if ((wv_m | at_m) != 0u) {
+    RV_LANES_BEGIN
+      VertexLoads V; v3 bpos[RV_MAXB]; m3 brot[RV_MAXB];
+#pragma unroll
+      for (int b = 0; b < RV_MAXB; ++b) hull_vertex_load(S, K, lane, b, (int)((wv_m >> b) & 1u), V);
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        const int item = lane + 64 * t, col = item < RV_NCOL * 8 ? item >> 3 : 0;
+        const unsigned long long kk = (col & 1) ? k1 : k0;
+        const int nd = (int)((at_m >> col) & 1u) | (((kk >> (RV_NMAN + RV_NCOL + (col >> 1))) & 0x8421ull) != 0ull);
+        box_vertex_load(S, K, lane, t, arm_on && item < RV_NCOL * 8 && nd, V);
+      }
+#pragma unroll
+      for (int b = 0; b < RV_MAXB; ++b) {
+        bpos[b] = ld3(S.e.body[b]);
+#pragma unroll
+        for (int k = 0; k < 9; ++k) brot[b].m[k] = S.s.rot[b][k];
+      }
+      vertex_stores(S, lane, V, bpos, brot);
+    RV_LANES_END
+  }
+#else
   {
     int any = 0;
 #pragma unroll
@@ -3666,6 +3898,7 @@ RV_DEV void sim_substep_heavy(Shared& S, const Consts& K) {
       RV_LANES_END
     }
   }
+#endif
   RV_PROF(18)
   {
     const int n_items = RV_UNI(S.s.n_items), n_list = RV_UNI(S.s.n_olist);

@@ -215,7 +215,8 @@ struct Scratch {
   int cn[RV_MAXB][RV_NCOL];
   int ow_run[RV_NMAN + RV_NCOL], olist[RV_NMAN + RV_NCOL], n_olist, n_items;
   QStage qst[4];                         // what the queries of the running round found, one slot per group
-  int wvneed[RV_MAXB];                   // body has hulls in a convex query of this substep
+  int wvneed[RV_MAXB];                   // body has hulls in a convex query of this substep (host emulation; the device keeps
+                                         // the mask in an SGPR and never touches these 16 B: the next LDS word wanted can replace them)
 #if !RV_ON_DEVICE
   int rowmap[120], n_rows;   // host emulation of the impulse-space solver: rows in visiting order
 #endif
