@@ -2184,40 +2184,95 @@ RV_DEV void solve_island_fingers(Shared& S, const Consts& K, const int X, const 
 // K.stop_after (profiling hook, 0 = off): return after a given phase group so that
 // per-phase costs can be read off as differences (tools/prof_phases.sh)
 // ---- arm phase groups (shared by the regular substep and the coasting path) ----
+#if RV_ON_DEVICE
+// What the joint lanes found, as wave-uniform masks in SGPRs (bit j: joint j): the joint state changed at all in this
+// substep; the joint moves faster than 1e-3.  The callers test these instead of reading nine LDS words each.
+struct JointMasks { unsigned chg, moving; };
+// The joint motors of the kinematic arm as ONE lane phase (loads first, stores last: DESIGN.md §10,
+// "LDS staging"): (a) per joint the raw commanded velocity and the factor that would bring it within its limit,
+// (b) the limb joints move synchronised -- one common scale, the smallest factor, keeps every commanded velocity
+// within its limit, so the path is a straight line in joint space.  The common scale is a 16-lane DPP min over the
+// limb lanes (the factors are positive floats, ordered like their bit patterns); the raw velocity and the scale stay
+// in the lane's registers.  Every lane runs the arithmetic (joint index clamped), the joint lanes store: the DPP reads
+// and the ballots are taken outside every branch.
+RV_DEV JointMasks arm_motor_lanes(Shared& S, const Consts& K, const int with_lq, const int count_step) {
+  const rv_config* c = K.cfg;
+  const rv_arm* arm = K.arm;
+  const int lane = (int)threadIdx.x;
+  DevEnv& e = S.e; const int j = lane < RV_NJ ? lane : RV_NJ - 1; const float dt = c->dt;
+  const int motor_on = e.motor_on[j], limb_dyn = c->limb_dynamics;
+  const float kp = e.motor_kp[j], mq = e.motor_q[j], vmax = e.vmax_cmd[j], qd0 = e.qd[j], q0 = e.q[j];
+  const float a_max = arm->a_max[j], q_lo = arm->q_lo[j], q_hi = arm->q_hi[j];
+  const int jq = j < RV_NLIMB ? j : 0;      // (the joint quaternion of a limb joint: index clamped for the fingers)
+  const q4 jquat = ldq(arm->jquat[jq]);
+  float travel = 0.0f; int steps0 = 0, steps1 = 0;
+  if (count_step == 1) { travel = S.s.jtravel[j]; steps0 = e.sim_steps; steps1 = e.substeps_last; }
+  if (count_step == 2) travel = S.s.ftravel[j];
+  // ---- arithmetic on the locals
+  float vdraw = 0.0f, ratio = 1.0f;
+  if (motor_on) {
+    vdraw = kp * (mq - q0) * (1.0f / dt);
+    float raw = fabsr(vdraw);
+    if (j < RV_NLIMB && raw > vmax) ratio = vmax / raw;
+  }
+  if (lane >= RV_NLIMB) ratio = 1.0f;
+  int r = __builtin_bit_cast(int, ratio);      // (<= 1: vmax / raw only where raw > vmax)
+  r = min(r, __builtin_amdgcn_update_dpp(0, r, 0x128, 0xf, 0xf, false));
+  r = min(r, __builtin_amdgcn_update_dpp(0, r, 0x124, 0xf, 0xf, false));
+  r = min(r, __builtin_amdgcn_update_dpp(0, r, 0x122, 0xf, 0xf, false));
+  r = min(r, __builtin_amdgcn_update_dpp(0, r, 0x121, 0xf, 0xf, false));
+  const float sync = __builtin_bit_cast(float, r);
+  float vd = 0.0f;
+  if (motor_on) {
+    vd = vdraw;
+    if (j < RV_NLIMB) vd = vd * sync;
+    vd = fclamp_pm(vd, vmax);
+  }
+  float dv = fclamp_pm(vd - qd0, a_max * dt);
+  float qd = qd0 + dv;
+  float qn = q0 + qd * dt;
+  if (qn < q_lo) { qn = q_lo; qd = 0.0f; }
+  if (qn > q_hi) { qn = q_hi; qd = 0.0f; }
+  q4 lq = jquat;
+  if (with_lq && j < RV_NLIMB) lq = joint_local_quat_of(jquat, qn);
+  travel += fabsr(qd) * dt;
+  JointMasks jm; jm.chg = 0; jm.moving = 0;
+  if (with_lq) {
+    jm.chg = (unsigned)__builtin_amdgcn_ballot_w64((qn != q0) || (qd != 0.0f)) & ((1u << RV_NJ) - 1u);   // did the joint state change at all?
+    jm.moving = (unsigned)__builtin_amdgcn_ballot_w64(fabsr(qd) > 1e-3f) & ((1u << RV_NJ) - 1u);
+  }
+  // ---- stores
+  if (lane < RV_NJ) {
+    if (j >= RV_NLIMB) { S.s.fing_dv[j - RV_NLIMB] = dv; S.s.fing_vt[j - RV_NLIMB] = vd; S.s.fing_qd0[j - RV_NLIMB] = qd; }
+    else if (limb_dyn) { S.s.limb_dv[j] = dv; S.s.limb_vt[j] = vd; S.s.limb_qd0[j] = qd; }
+    e.q[j] = qn; e.qd[j] = qd;
+    if (with_lq && j < RV_NLIMB) stq(S.s.lq[j], lq);
+    if (count_step == 1) {
+      S.s.jtravel[j] = travel;      // coasting: path length of the joint
+      if (j == 0) { e.sim_steps = steps0 + 1; e.substeps_last = steps1 + 1; }
+    }
+    if (count_step == 2) S.s.ftravel[j] = travel;   // an "arm far" substep: the boxes are not recomputed
+  }
+  RV_WAVE_SYNC();
+  return jm;
+}
+#endif
 // ControllableBody.update + joint motors.  with_lq: also the local joint quaternions
 // of the new positions and the per-joint "moving" flags (input of the FK phases).
 // count_step: lane 0 advances the step counters (coasting substeps end here).
 RV_DEV void arm_motor_phases(Shared& S, const Consts& K, const int with_lq, const int count_step) {
+#if RV_ON_DEVICE
+  control_update_phases(S, K);
+  (void)arm_motor_lanes(S, K, with_lq, count_step);
+#else
   const rv_config* c = K.cfg;
   const rv_arm* arm = K.arm;
   control_update_phases(S, K);
   // joint motors of the kinematic arm, (a) per joint: the raw
   // commanded velocity and the factor that would bring it within its limit
-#if RV_ON_DEVICE
-  {
-    // (a) + (b) in one phase: the common scale is a 16-lane DPP min over the limb lanes (the
-    // factors are positive floats, ordered like their bit patterns)
-    const int lane = (int)threadIdx.x;
-    const DevEnv& e0 = S.e; const int j0 = lane < RV_NJ ? lane : RV_NJ - 1;
-    float vd0 = 0.0f, ratio0 = 1.0f;
-    if (e0.motor_on[j0]) {
-      vd0 = e0.motor_kp[j0] * (e0.motor_q[j0] - e0.q[j0]) * (1.0f / c->dt);
-      float raw = fabsr(vd0);
-      if (j0 < RV_NLIMB && raw > e0.vmax_cmd[j0]) ratio0 = e0.vmax_cmd[j0] / raw;
-    }
-    if (lane >= RV_NLIMB) ratio0 = 1.0f;
-    int r = __builtin_bit_cast(int, ratio0);      // (<= 1: vmax / raw only where raw > vmax)
-    r = min(r, __builtin_amdgcn_update_dpp(0, r, 0x128, 0xf, 0xf, false));
-    r = min(r, __builtin_amdgcn_update_dpp(0, r, 0x124, 0xf, 0xf, false));
-    r = min(r, __builtin_amdgcn_update_dpp(0, r, 0x122, 0xf, 0xf, false));
-    r = min(r, __builtin_amdgcn_update_dpp(0, r, 0x121, 0xf, 0xf, false));
-    if (lane < RV_NJ) { S.s.vdraw[lane] = vd0; S.s.ratio[lane] = __builtin_bit_cast(float, r); }
-  }
-#else
 #define RV_EMU_SECTION 3
 #include "../../tests/emu/rv_emu_hooks.h"      // host lane emulation (test scaffolding; not compiled into the product)
 #undef RV_EMU_SECTION
-#endif
   // (b) limb joints move synchronised: one common scale (the smallest factor)
   // keeps every commanded velocity within its limit, so the path is a straight
   // line in joint space.
@@ -2226,12 +2281,8 @@ RV_DEV void arm_motor_phases(Shared& S, const Consts& K, const int with_lq, cons
       // (loads first, stores last: DESIGN.md §10, "LDS staging")
       DevEnv& e = S.e; int j = lane; float dt = c->dt;
       float sync = 1.0f;
-#if RV_ON_DEVICE
-      sync = S.s.ratio[j];      // (its own store: the common scale)
-#else
 #pragma unroll
       for (int k = 0; k < RV_NLIMB; ++k) sync = fminr(sync, S.s.ratio[k]);
-#endif
       const int motor_on = e.motor_on[j], limb_dyn = c->limb_dynamics;
       const float vdraw = S.s.vdraw[j], vmax = e.vmax_cmd[j], qd0 = e.qd[j], q0 = e.q[j];
       const float a_max = arm->a_max[j], q_lo = arm->q_lo[j], q_hi = arm->q_hi[j];
@@ -2271,8 +2322,24 @@ RV_DEV void arm_motor_phases(Shared& S, const Consts& K, const int with_lq, cons
       if (count_step == 2) S.s.ftravel[j] = travel;   // an "arm far" substep: the boxes are not recomputed
     }
   RV_LANES_END
+#endif
 }
 // local joint quaternions / moving flags from the stored joint state (kinematics refresh)
+#if RV_ON_DEVICE
+// (every lane runs the arithmetic, joint index clamped; the "moving" flags leave as a ballot: see JointMasks)
+RV_DEV unsigned arm_lq_lanes(Shared& S, const Consts& K) {
+  const int lane = (int)threadIdx.x;
+  const DevEnv& e = S.e; const int j = lane < RV_NJ ? lane : RV_NJ - 1;
+  const float qd = e.qd[j], q = e.q[j];
+  const q4 jquat = ldq(K.arm->jquat[j < RV_NLIMB ? j : 0]);
+  q4 lq = jquat;
+  if (j < RV_NLIMB) lq = joint_local_quat_of(jquat, q);
+  const unsigned moving = (unsigned)__builtin_amdgcn_ballot_w64(fabsr(qd) > 1e-3f) & ((1u << RV_NJ) - 1u);
+  if (lane < RV_NLIMB) stq(S.s.lq[j], lq);
+  RV_WAVE_SYNC();
+  return moving;
+}
+#else
 RV_DEV void arm_lq_phase(Shared& S, const Consts& K) {
   RV_LANES_BEGIN
     if (lane < RV_NJ) {
@@ -2286,8 +2353,14 @@ RV_DEV void arm_lq_phase(Shared& S, const Consts& K) {
     }
   RV_LANES_END
 }
+#endif
 // forward kinematics from the local joint quaternions S.s.lq
+// (device: moving_m is the "moving" mask of the phase that wrote them -- arm_motor_lanes, arm_lq_lanes)
+#if RV_ON_DEVICE
+RV_DEV void arm_fk_phases(Shared& S, const Consts& K, const unsigned moving_m) {
+#else
 RV_DEV void arm_fk_phases(Shared& S, const Consts& K) {
+#endif
   const rv_arm* arm = K.arm;
   // (a) lane 0: the serial product of the joint quaternions
   RV_LANES_BEGIN
@@ -2304,10 +2377,14 @@ RV_DEV void arm_fk_phases(Shared& S, const Consts& K) {
 #pragma unroll
       for (int i = 0; i <= RV_NLIMB; ++i) stq(e.fquat[i], fq[i]);
     } else if (lane == 1) {
+#if RV_ON_DEVICE
+      S.s.arm_moving = moving_m != 0;
+#else
       int mv = 0;
 #pragma unroll
       for (int j = 0; j < RV_NJ; ++j) mv |= S.s.jmoving[j];
       S.s.arm_moving = mv;
+#endif
     }
   RV_LANES_END
   // (b) lanes 0-7: each link's offset rotated into the world, joint axis, rotation matrix
@@ -2353,6 +2430,16 @@ RV_DEV void arm_fk_phases(Shared& S, const Consts& K) {
       st3(e.fpos[lane], p);
     }
   RV_LANES_END
+}
+// the link frames of the stored joint state
+RV_DEV void arm_lq_fk_phases(Shared& S, const Consts& K) {
+#if RV_ON_DEVICE
+  const unsigned moving_m = arm_lq_lanes(S, K);
+  arm_fk_phases(S, K, moving_m);
+#else
+  arm_lq_phase(S, K);
+  arm_fk_phases(S, K);
+#endif
 }
 // collider boxes in the world: centres, AABBs (centre +- |R| half: no vertices needed) and the arm-table gate.
 // The eight vertices of a box are only the input of a convex query: arm_box_vertices() computes them for the
@@ -2417,8 +2504,10 @@ RV_DEV void arm_collider_phases(Shared& S, const Consts& K, const int arm_on) {
       S.s.atflag[col] = atflag;
       S.s.coltravel[col] = tr * 1.02f + 1e-7f;
     }
+#if !RV_ON_DEVICE      // (the device keeps the wake test's flags in wave masks: sim_substep_light)
     if (lane >= 16 && lane < 16 + RV_MAXB) { S.s.wake[lane - 16] = 0; S.s.bnear[lane - 16] = 0; }
     if (lane == 24) S.s.near_any = 0;
+#endif
     // (no arm in this substep -- the bodies settling after a reset: the boxes do not travel.  The wake test reads the travel
     // whatever arm_on is and keeps its distance bounds; in a launch that BEGINS with a reset nothing had written it yet, and a
     // negative left-over in LDS turned the bounds into "far away for ever" -- found by the poisoned-LDS build, round 5)
@@ -3188,8 +3277,7 @@ RV_DEV int coast_fused(Shared& S, const Consts& K, const int steps_check, const 
 }
 // frames, colliders and AABBs of the current joint state (after coasting)
 RV_DEV void arm_refresh_kinematics(Shared& S, const Consts& K) {
-  arm_lq_phase(S, K);
-  arm_fk_phases(S, K);
+  arm_lq_fk_phases(S, K);
   arm_collider_phases(S, K, 1);
 }
 // up to `want` coasted substeps with the fused loop; the kinematics are measured again whenever the
@@ -3258,14 +3346,45 @@ RV_DEV int sim_substep_light(Shared& S, const Consts& K) {
   // needs the frames (kin_fresh = 0).  Exact: every skipped test would have said "no".  (Without deactivation --
   // the reference's most likely semantics -- the arm is far in ~80 % of the substeps.)
   int far = 0;
+#if RV_ON_DEVICE
+  // The flags of this substep, read ONCE (as in the heavy part's preparation): every lane loads the flag words of body
+  // (lane & 3), the point count of that body's arm manifold and of pair manifold min(lane, 5) -- loads first, no short
+  // circuit -- and ballots taken by the whole wave turn them into wave-uniform masks in SGPRs (bit b: body b; bit k:
+  // pair k).  The phases below test bits of these instead of calling body_present / body_on / body_static, whose `&&`
+  // chains are one exposed LDS round trip and one exec-mask nest per word.  Nothing changes a flag before the
+  // body-velocity phase, which folds its wake-ups in (woken_m).
+  static_assert(RV_MAXB == 4 && RV_NBB == 6, "flag masks: body lane & 3, pair min(lane, 5)");
+  unsigned present_m, asleep_m, static_m, on_m, armpts_m, tied_m, pairpts_m, mover_m;
+  {
+    const int lane = (int)threadIdx.x;
+    const DevEnv& e = S.e;
+    const int bl = lane & 3, kl = lane < RV_NBB ? lane : RV_NBB - 1;
+    const int l_act = e.active[bl], l_frz = e.frozen[bl], l_slp = e.asleep[bl], l_sc = e.sleep_count[bl], l_st = e.still_count[bl];
+    const int l_con = e.con_on[bl], l_an = e.man[RV_AIDX(bl)].n, l_pn = e.man[RV_BBIDX(kl)].n;
+    const float l_im = e.inv_mass[bl];
+    present_m = (unsigned)__builtin_amdgcn_ballot_w64((l_act != 0) & (l_frz == 0)) & 15u;
+    asleep_m = (unsigned)__builtin_amdgcn_ballot_w64(l_slp != 0) & 15u;
+    static_m = (unsigned)__builtin_amdgcn_ballot_w64(l_im == 0.0f) & 15u;
+    on_m = present_m & ~asleep_m;
+    armpts_m = (unsigned)__builtin_amdgcn_ballot_w64(l_an != 0) & 15u;                                                // the arm manifold has points
+    tied_m = (unsigned)__builtin_amdgcn_ballot_w64((RV_CON_TYPE(l_con) != 0) & (RV_CON_CHILD(l_con) >= RV_MAXB)) & 15u;   // tied to a LINK
+    pairpts_m = (unsigned)__builtin_amdgcn_ballot_w64(l_pn != 0) & ((1u << RV_NBB) - 1u);                             // the pair manifold has points
+    mover_m = on_m & ~((unsigned)__builtin_amdgcn_ballot_w64((l_sc > 0) | (l_st >= 50)) & 15u);                       // a MOVING neighbour (wake stage 1)
+  }
+  JointMasks jm; jm.chg = 0; jm.moving = 0;
+#endif
   if (arm_on && K.stop_after == 0 && S.s.far_valid && !c->finger_dynamics && !c->limb_dynamics) {
     int ok = 0;
+#if RV_ON_DEVICE
+    ok = on_m != 0 && armpts_m == 0 && tied_m == 0;      // (a body tied to a LINK: the frames are needed)
+#else
 #pragma unroll
     for (int b = 0; b < RV_MAXB; ++b) ok |= body_on(S.e, b);
 #pragma unroll
     for (int b = 0; b < RV_MAXB; ++b) if (S.e.man[RV_AIDX(b)].n != 0) ok = 0;
 #pragma unroll
     for (int b = 0; b < RV_MAXB; ++b) if (RV_CON_TYPE(S.e.con_on[b]) != 0 && RV_CON_CHILD(S.e.con_on[b]) >= RV_MAXB) ok = 0;   // (a body tied to a LINK: the frames are needed)
+#endif
     if (ok) {
       int near_any = 0;
       RV_LANES_BEGIN
@@ -3283,8 +3402,13 @@ RV_DEV int sim_substep_light(Shared& S, const Consts& K) {
 #pragma unroll
           for (int x = 0; x < 3; ++x) { lo[x] = S.s.colmin[col][x] - T; hi[x] = S.s.colmax[col][x] + T; }
           if (isb) {
+#if RV_ON_DEVICE
+            if (((present_m & ~static_m) >> b) & 1u) {      // (a static body has no business with the arm)
+              if ((asleep_m >> b) & 1u) {
+#else
             if (body_present(e, b) && !body_static(e, b)) {      // (a static body has no business with the arm)
               if (e.asleep[b]) {
+#endif
                 const float r = wake_range(e, arm, c, b, col) + 2.0f * c->margin;
                 near = aabb_aabb_dist2(e.baabb[b], e.baabb[b] + 3, lo, hi) < r * r;
               }
@@ -3315,30 +3439,47 @@ RV_DEV int sim_substep_light(Shared& S, const Consts& K) {
     arm_motor_phases(S, K, 0, 2);
     RV_PROF(40)
     RV_LANES_BEGIN
+#if !RV_ON_DEVICE      // (the device keeps the wake test's flags in wave masks)
       if (lane < RV_MAXB) { S.s.wake[lane] = 0; S.s.bnear[lane] = 0; }
       if (lane == 8) S.s.near_any = 0;
+#endif
       if (lane == 9) S.s.arm_moving = 0;
       if (lane >= 16 && lane < 16 + RV_NCOL) { S.s.colflag[lane - 16] = 0; S.s.atflag[lane - 16] = 0; }
       if (lane == 63) { S.s.kin_fresh = 0; S.s.clr_valid = 0; S.s.far = 1; S.s.far_n = S.s.far_n + 1; }
     RV_LANES_END
   } else
   if (arm_on) {
+#if RV_ON_DEVICE
+    control_update_phases(S, K);
+    jm = arm_motor_lanes(S, K, 1, 0);
+#else
     arm_motor_phases(S, K, 1, 0);
+#endif
     RV_PROF(40)
     RV_STOPL(12)
     if (S.s.kin_fresh && K.stop_after == 0) {
+#if RV_ON_DEVICE
+      arm_static = jm.chg == 0;
+#else
       arm_static = 1;
 #pragma unroll
       for (int j = 0; j < RV_NJ; ++j) if (S.s.jchg[j]) arm_static = 0;
+#endif
     }
+#if RV_ON_DEVICE
+    if (!arm_static) arm_fk_phases(S, K, jm.moving);
+#else
     if (!arm_static) arm_fk_phases(S, K);
+#endif
   }
   RV_PROF(41)
   RV_STOPL(1)
   if (arm_static) {
     RV_LANES_BEGIN
+#if !RV_ON_DEVICE
       if (lane < RV_MAXB) { S.s.wake[lane] = 0; S.s.bnear[lane] = 0; }
       if (lane == 8) S.s.near_any = 0;
+#endif
       if (lane == 9) S.s.arm_moving = 0;
       if (lane >= 16 && lane < 16 + RV_NCOL) { S.s.colflag[lane - 16] = 0; S.s.coltravel[lane - 16] = 0.0f * 1.02f + 1e-7f; }
       if (lane == 63) S.s.clr_valid = 0;
@@ -3354,6 +3495,57 @@ RV_DEV int sim_substep_light(Shared& S, const Consts& K) {
   // the body's hulls (= when a contact point would be created).  Stage 1, one lane
   // per (body, box) and per ordered (body, neighbour) pair: boxes whose AABB is
   // within that distance of the sleeper's cached AABB are flagged for stage 2.
+#if RV_ON_DEVICE
+  // Straight-line code (loads first, stores last: DESIGN.md §10, "LDS staging"): every lane loads what a (body, box)
+  // lane and what a neighbour lane reads, through clamped indices; the predicates are bits of the flag masks; the
+  // flags leave as ballots.  nr_m bit RV_NCOL b + col: box col is flagged for sleeper b; wake_m bit b: body b wakes.
+  static_assert(RV_MAXB * RV_NCOL + RV_MAXB * (RV_MAXB - 1) <= 64 && RV_MAXB * 16 == 64, "wake test: one lane per (body, box) and per ordered pair; one 16-lane group per body");
+  const int arm_moving_u = arm_on && !far && !arm_static && jm.moving != 0;      // (= arm_on && S.s.arm_moving)
+  unsigned long long nr_m; unsigned wake_m = 0, bnear_m = 0, colnear_m = 0;
+  {
+    const int lane = (int)threadIdx.x;
+    const DevEnv& e = S.e;
+    const int is_bc = lane < RV_MAXB * RV_NCOL, is_nb = !is_bc && lane < RV_MAXB * RV_NCOL + RV_MAXB * (RV_MAXB - 1);
+    const int t = is_nb ? lane - RV_MAXB * RV_NCOL : 0;
+    const int b = is_bc ? lane / RV_NCOL : t / (RV_MAXB - 1);
+    const int col = is_bc ? lane - b * RV_NCOL : 0;
+    int a = is_nb ? t - b * (RV_MAXB - 1) : 0;
+    if (is_nb && a >= b) a++;
+    const float sep0 = S.s.sep[b][col], ctravel = S.s.coltravel[col], margin = c->margin;
+    const int far_n = S.s.far_n;
+    const float wr = wake_range(e, K.arm, c, b, col);
+    const float d2 = aabb_aabb_dist2(e.baabb[b], e.baabb[b] + 3, S.s.colmin[col], S.s.colmax[col]);
+    const v3 pa = ld3(e.body[a]), pb = ld3(e.body[b]);
+    const float rad_a = e.radius[a], rad_b = e.radius[b], bbb = brk_bb(e, c, a, b);
+    // ---- arithmetic on the locals
+    // sep: a lower bound of (hull distance - contact range) left over from the last
+    // distance query, minus the box's travel since (a sleeper does not move); while it
+    // is positive the query cannot hit and is skipped.  Exact: only the work changes.
+    float sep = sep0 - ctravel;
+    if (far_n != 0) sep = 0.0f;        // ("arm far" substeps did not keep the bound up to date: it starts again)
+    const float r = wr + 2.0f * margin;
+    const unsigned sleeper_b = ((present_m & asleep_m) >> b) & 1u;
+    const int nr = is_bc & arm_moving_u & (int)(sleeper_b & ~(static_m >> b)) & (d2 < r * r) & !(sep > 0.0f);
+    // only a MOVING neighbour wakes a sleeper (resting neighbours would ping-pong)
+    // ... and moving means: left its 1 mm pose window within the last 50 substeps
+    const v3 d = sub(pa, pb);
+    const float rr = rad_a + rad_b + bbb;
+    const int nbw = is_nb & (int)(sleeper_b & (mover_m >> a)) & (dot(d, d) < rr * rr);
+    nr_m = __builtin_amdgcn_ballot_w64(nr != 0);
+    const unsigned long long nb_m = __builtin_amdgcn_ballot_w64(nbw != 0) >> (RV_MAXB * RV_NCOL);
+#pragma unroll
+    for (int x = 0; x < RV_MAXB; ++x) {
+      const unsigned nrx = (unsigned)(nr_m >> (RV_NCOL * x)) & ((1u << RV_NCOL) - 1u);
+      bnear_m |= (unsigned)(nrx != 0) << x;
+      colnear_m |= nrx;
+      wake_m |= (unsigned)(((unsigned)(nb_m >> ((RV_MAXB - 1) * x)) & ((1u << (RV_MAXB - 1)) - 1u)) != 0) << x;
+    }
+    // ---- stores
+    if (is_bc) S.s.sep[b][col] = sep > 0.0f ? sep : 0.0f;
+  }
+  RV_WAVE_SYNC();
+  const int near_any = nr_m != 0;
+#else
   RV_LANES_BEGIN
     const DevEnv& e = S.e;
     if (lane < RV_MAXB * RV_NCOL) {
@@ -3386,18 +3578,27 @@ RV_DEV int sim_substep_light(Shared& S, const Consts& K) {
     }
   RV_LANES_END
   const int near_any = S.s.near_any;
+#endif
   if (near_any) {
     // stage 2a: world hull vertices of the flagged sleepers, and the vertices of the boxes near them
     RV_LANES_BEGIN
       VertexLoads V; v3 bpos[RV_MAXB]; m3 brot[RV_MAXB];
 #pragma unroll
+#if RV_ON_DEVICE
+      for (int b = 0; b < RV_MAXB; ++b) hull_vertex_load(S, K, lane, b, (bnear_m >> b) & 1u, V);
+#else
       for (int b = 0; b < RV_MAXB; ++b) hull_vertex_load(S, K, lane, b, S.s.bnear[b], V);
+#endif
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
         const int item = lane + 64 * t, col = item < RV_NCOL * 8 ? item >> 3 : 0;
+#if RV_ON_DEVICE
+        const int nd = (colnear_m >> col) & 1u;
+#else
         int nd = 0;
 #pragma unroll
         for (int b = 0; b < RV_MAXB; ++b) nd |= S.s.nearf[b][col];
+#endif
         box_vertex_load(S, K, lane, t, item < RV_NCOL * 8 && nd, V);
       }
 #pragma unroll
@@ -3405,17 +3606,26 @@ RV_DEV int sim_substep_light(Shared& S, const Consts& K) {
       vertex_stores(S, lane, V, bpos, brot);
     RV_LANES_END
     // stage 2b: one 16-lane group per body runs the distance queries, box by box
+#if RV_ON_DEVICE
+    int hit = 0;      // (the same in the sixteen lanes of a group; balloted after the groups have converged again)
+#endif
     RV_LANES_BEGIN
       const DevEnv& e = S.e;
       const int b = lane >> 4;
-#if !RV_ON_DEVICE
+#if RV_ON_DEVICE
+      const unsigned nrb = (unsigned)(nr_m >> (RV_NCOL * b)) & ((1u << RV_NCOL) - 1u);      // the flagged boxes of this group's body
+      if (nrb != 0 && !((wake_m >> b) & 1u)) {
+        const float mg = c->margin;
+        for (int col = 0; col < RV_NCOL && !hit; ++col) {
+          if (!((nrb >> col) & 1u)) continue;
+#else
       if ((lane & 15) != 0) continue;   // host emulation: one lane per group does the work
-#endif
       if (S.s.bnear[b] && !S.s.wake[b]) {
         const float mg = c->margin;
         int hit = 0;
         for (int col = 0; col < RV_NCOL && !hit; ++col) {
           if (!S.s.nearf[b][col]) continue;
+#endif
           const float brk = wake_range(e, K.arm, c, b, col);
           v3 d = sub(ld3(e.body[b]), ld3(S.s.colc[col]));
           float lbmin = 1e30f;
@@ -3427,9 +3637,18 @@ RV_DEV int sim_substep_light(Shared& S, const Consts& K) {
           }
           if (!hit && (lane & 15) == 0) S.s.sep[b][col] = fmaxr(lbmin - 2.0f * mg - brk - 1e-5f, 0.0f);
         }
+#if !RV_ON_DEVICE
         if (hit) S.s.wake[b] = 1;
+#endif
       }
     RV_LANES_END
+#if RV_ON_DEVICE
+    {
+      const unsigned long long hit_m = __builtin_amdgcn_ballot_w64(hit != 0);
+#pragma unroll
+      for (int x = 0; x < RV_MAXB; ++x) wake_m |= (unsigned)((hit_m >> (16 * x)) & 1ull) << x;
+    }
+#endif
   }
   RV_PROF(43)
   RV_STOPL(17)
@@ -3439,6 +3658,25 @@ RV_DEV int sim_substep_light(Shared& S, const Consts& K) {
   // sleeper that shares a manifold holding points with a body that is awake, or is being woken,
   // wakes as well -- otherwise that manifold would not be solved and the awake body would lose its
   // support.  Every body lane works the closure out for itself.
+#if RV_ON_DEVICE
+  // (the device works the closure out once, in scalar arithmetic on the masks and only when somebody wakes: the same rule
+  // over the six pairs in the same three passes.  woken_m bit b: body b wakes in this substep.)
+  unsigned woken_m = wake_m;
+  if (wake_m != 0) {
+    unsigned aw = on_m | wake_m;
+#pragma unroll
+    for (int pass = 0; pass < 3; ++pass)
+#pragma unroll
+      for (int k = 0; k < RV_NBB; ++k) {
+        const unsigned pair = (1u << bb_a(k)) | (1u << bb_b(k));
+        if ((present_m & pair) == pair && ((pairpts_m >> k) & 1u) && (aw & pair) != 0) aw |= pair;
+      }
+    woken_m |= aw & present_m & asleep_m;
+  }
+  unsigned at_m = 0;      // bit col: S.s.atflag[col] (none: arm off)
+  RV_LANES_BEGIN
+    const int at_l = S.s.atflag[lane < RV_NCOL ? lane : 0];
+#else
   int wake_me = 0;
   RV_LANES_BEGIN
     if (lane < RV_MAXB) {
@@ -3466,13 +3704,8 @@ RV_DEV int sim_substep_light(Shared& S, const Consts& K) {
 #pragma unroll
         for (int x = 0; x < RV_MAXB; ++x) if (x == lane) me = aw[x] && pr[x] && e.asleep[x];
       }
-#if RV_ON_DEVICE
-      wake_me = me;
-#else
       S.s.ready[lane] = me;      // (host emulation: lane-local values do not survive the phase)
-#endif
     }
-#if !RV_ON_DEVICE
   RV_LANES_END
   RV_LANES_BEGIN
 #endif
@@ -3480,13 +3713,17 @@ RV_DEV int sim_substep_light(Shared& S, const Consts& K) {
     if (lane == 6) { S.s.far = far; if (!far) S.s.far_n = 0; }
     if (lane < RV_MAXB) {
       int b = lane; DevEnv& e = S.e;
-#if !RV_ON_DEVICE
-      wake_me = S.s.ready[lane];
-#endif
       // (loads first, stores last: DESIGN.md §10, "LDS staging".  The wake-up writes e.asleep, which body_on reads: forwarded)
+#if RV_ON_DEVICE
+      const int woken = (woken_m >> b) & 1u;
+      const int present = (present_m >> b) & 1u, asleep0 = (asleep_m >> b) & 1u;
+      const int is_static = (static_m >> b) & 1u;
+#else
+      wake_me = S.s.ready[lane];
       const int woken = S.s.wake[b] || wake_me;
       const int present = e.active[b] && !e.frozen[b], asleep0 = e.asleep[b];
       const int is_static = body_static(e, b);
+#endif
       float bs[13];
 #pragma unroll
       for (int k = 0; k < 13; ++k) bs[k] = e.body[b][k];
@@ -3529,18 +3766,28 @@ RV_DEV int sim_substep_light(Shared& S, const Consts& K) {
         for (int k = 0; k < 9; ++k) S.s.iinv[b][k] = iinv[k];
       }
     }
+#if RV_ON_DEVICE
+    at_m = (unsigned)__builtin_amdgcn_ballot_w64(at_l != 0) & ((1u << RV_NCOL) - 1u);
+#endif
   RV_LANES_END
   RV_STOPL(18)
 
   // uniform: is any body awake?  can any arm collider be within the contact-query
   // distance of the table top?
   int any_on = 0, at_possible = 0;
+#if RV_ON_DEVICE
+  // (the flags as the body-velocity phase left them: a body that was woken is no longer asleep; the table flags were
+  // loaded by that phase, one word per lane -- the collider phase, or the far branch, wrote them before it)
+  any_on = (present_m & ~(asleep_m & ~woken_m)) != 0;
+  if (arm_on) at_possible = at_m != 0;
+#else
 #pragma unroll
   for (int b = 0; b < RV_MAXB; ++b) any_on |= body_on(S.e, b);
   if (arm_on) {
 #pragma unroll
     for (int col = 0; col < RV_NCOL; ++col) at_possible |= S.s.atflag[col];
   }
+#endif
   // quiet substep: every body asleep (or absent) and no arm collider near the
   // table -> nothing to collide, solve or integrate
   if (!any_on && !at_possible) {
@@ -4253,7 +4500,7 @@ RV_DEV void sim_substep_heavy(Shared& S, const Consts& K) {
 #include "../../tests/emu/rv_emu_hooks.h"      // host lane emulation (test scaffolding; not compiled into the product)
 #undef RV_EMU_SECTION
 #endif
-  if (limb) { arm_lq_phase(S, K); arm_fk_phases(S, K); }   // the link frames follow the solved joint state
+  if (limb) arm_lq_fk_phases(S, K);   // the link frames follow the solved joint state
   // an island of three or four bodies (there can be only one): velocity-space Gauss-Seidel in the
   // order  bodies (their table and arm points), then the three rounds of body pairs.  Bodies do
   // not share anything in the first stage and the two pairs of a round touch disjoint bodies, so

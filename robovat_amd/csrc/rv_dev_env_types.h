@@ -160,7 +160,7 @@ struct Scratch {
   float poses[RV_MAXB][7];
   int num_waypoints, interrupt, has_budget, max_phase_steps;
   int loop_break, wus_steps, wus_stable, valid;
-  int wake[RV_MAXB];
+  int wake[RV_MAXB];                     // wake test -> body-velocity phase (host emulation; the device keeps a mask in an SGPR)
   // budget of the running sim_run (rv_step_poll): at most bud_sub substeps / bud_clk shader
   // clocks from bud_t0 in this launch (0 = no limit); suspended: the call returned on the budget
   int bud_sub, bud_sub0, suspended, wus_resume;
@@ -172,7 +172,7 @@ struct Scratch {
   // ControllableBody._update_ik as a wave-wide solve: seed / solution, Jacobian, flags
   float ik_q[RV_NLIMB], ik_J[6][RV_NLIMB]; int ik_need, ik_conv;
   float lq[RV_NLIMB][4];
-  float vdraw[RV_NJ], ratio[RV_NJ];      // motor phase: raw commanded velocity, limit factor
+  float vdraw[RV_NJ], ratio[RV_NJ];      // motor phase: raw commanded velocity, limit factor (host emulation; registers on the device)
   float fing_dv[2], fing_vt[2], fing_qd0[2];   // finger motors this substep: velocity step taken, commanded velocity, velocity after it
   // limb dynamics (rv_config.limb_dynamics): the same of the limb joints; centres of mass, joint-space
   // inertia, the Gauss-Jordan workspace [M | 1] -> [. | M^-1], generalised gravity force, motor-row bounds
@@ -185,7 +185,7 @@ struct Scratch {
   // e_j and column j of M^-1.  The one-lane system solver, which takes the cases with several awake bodies, derives
   // the rows of a point when it visits it: limb_point_row)
   float lJa[12 + RV_NLIMB][RV_NLIMB], lMiJ[12 + RV_NLIMB][RV_NLIMB], linvk[12];
-  int jmoving[RV_NJ], jchg[RV_NJ];
+  int jmoving[RV_NJ], jchg[RV_NJ];       // joint moves / changed at all in this substep (host emulation; JointMasks on the device)
   float rvec[RV_NLIMB + 1][3];           // FK: link offsets rotated into the world
   int jt_applied;                        // the motor targets hold the current joint target (per launch)
   int atflag[RV_NCOL];                   // collider box may be within the contact-query distance of the table
@@ -193,7 +193,7 @@ struct Scratch {
   // "arm far" substeps (sim_substep_light): joint path lengths since the collider boxes were last computed, whether
   // those boxes exist at all in this launch, substeps taken far since then, and this substep's verdict
   float ftravel[RV_NJ]; int far_valid, far_n, far;
-  int nearf[RV_MAXB][RV_NCOL], bnear[RV_MAXB], near_any;   // wake test stage 1 -> stage 2
+  int nearf[RV_MAXB][RV_NCOL], bnear[RV_MAXB], near_any;   // wake test stage 1 -> stage 2 (host emulation; ballots on the device)
   float sep[RV_MAXB][RV_NCOL], coltravel[RV_NCOL];          // distance-bound culling of the wake queries
   float cdelta[3][RV_NCOL];                                 // coasting: box travel bound per candidate length
   float clr_t[RV_NCOL], clr_b[RV_NCOL]; int clr_valid;      // coasting: clearances left (table, bodies)
