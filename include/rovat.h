@@ -716,6 +716,60 @@ int  rv_depth_noise(rv_world* w, const rv_depth_noise_params* h_params, const fl
                     float* d_depth_out /* may be d_depth_in */, float* d_gamma /* [N] or NULL */,
                     uint8_t* d_applied /* [N] or NULL */, float* d_grid /* [N][H/R][W/R] or NULL */);
 
+/* ---- point clouds as the real sensor's branch of the reference segments them (camera_obs.py:90-124, 182-211): a plane
+ *      fit that removes the table, DBSCAN on what is left, the C largest clusters sampled to P points each.  The three
+ *      stages, their arithmetic and the Philox words are written out in csrc/rv_dev_segment.h.  Both
+ *      calls work on a CHUNK of the world's envs, env_first .. env_first + env_count - 1, so that the caller bounds the
+ *      [env_count][M][3] scratch; the draws are keyed by the global env id, not by the chunk.  Neither reads more of an
+ *      env than its camera and its global id, neither changes env state; asynchronous on the world's stream.
+ *      rv_deproject: every pixel of d_depth ([env_count][cam_height][cam_width], eye z) through Camera.deproject_pixel
+ *      with the env's own calibration (rv_get_camera) into d_points [env_count][H * W][3]; d_valid [env_count][H * W] = 1
+ *      where depth > 0 and the point is inside the config's crop (always, without a crop).
+ *      rv_segment_cloud: d_points [env_count][M][3], d_valid [env_count][M] or NULL (all valid; a point with a non-finite
+ *      coordinate is invalid either way).  Outputs: d_labels [env_count][M] (RV_SEG_INVALID, RV_SEG_PLANE, RV_SEG_SKIPPED,
+ *      -1 = noise, >= 0 = cluster number), d_clouds [env_count][C][P][3], d_slot_labels / d_slot_counts [env_count][C] (the
+ *      cluster number, -1 for an empty slot, and its member count), d_plane [env_count][4] (the unnormalised normal and the
+ *      offset: n . p + d = 0 on the plane), d_info [env_count][RV_SEG_INFO_WORDS].  At most RV_SEG_MAXPTS survivors of the
+ *      plane stage are clustered (more: that many evenly spaced, the rest RV_SEG_SKIPPED, RV_SEG_FLAG_OVERFLOW; min_samples
+ *      is not rescaled).  RV_ERR_VALUE, with nothing launched: a NULL params or required buffer, a buffer that is not
+ *      4-byte aligned, an env range outside the world, M outside [1, 2^24], num_hypotheses outside [0,
+ *      RV_SEG_MAX_HYPOTHESES], num_clusters outside [1, RV_SEG_MAXSLOTS], num_points outside [1, 65536], eps or
+ *      plane_thresh non-positive or non-finite, min_samples < 1, draw_index outside [0, 2^32). ---- */
+#define RV_SEG_MAXPTS 8192
+#define RV_SEG_MAX_HYPOTHESES 1024
+#define RV_SEG_MAXSLOTS 16
+#define RV_SEG_MAX_POINTS 65536
+#define RV_SEG_INVALID (-3)
+#define RV_SEG_PLANE   (-2)
+#define RV_SEG_SKIPPED (-4)
+#define RV_SEG_INFO_WORDS 8
+#define RV_SEG_INFO_VALID 0      /* valid points                                  */
+#define RV_SEG_INFO_PLANE 1      /* of them on the plane                          */
+#define RV_SEG_INFO_SURVIVORS 2  /* valid, not on the plane                       */
+#define RV_SEG_INFO_KEPT 3       /* of them clustered (<= RV_SEG_MAXPTS)          */
+#define RV_SEG_INFO_CLUSTERS 4   /* clusters DBSCAN found                         */
+#define RV_SEG_INFO_NOISE 5      /* kept points labelled -1                       */
+#define RV_SEG_INFO_BEST_H 6     /* the winning hypothesis, -1: none              */
+#define RV_SEG_INFO_FLAGS 7
+#define RV_SEG_FLAG_NO_PLANE 1   /* T = 0, fewer than 3 valid points or every hypothesis void */
+#define RV_SEG_FLAG_OVERFLOW 2   /* more than RV_SEG_MAXPTS survivors             */
+#define RV_SEG_FLAG_BOUND 4      /* a loop bound ran out (never seen; the labels are then not to be trusted) */
+#define RV_SEG_FLAG_FEWER 8      /* fewer clusters than slots: bodies merged, hidden or too small */
+typedef struct rv_segment_params {
+  int32_t num_hypotheses;      /* T in [0, RV_SEG_MAX_HYPOTHESES]; 0: no plane stage */
+  float   plane_thresh;        /* > 0: the half width of the plane's band (m)  */
+  float   eps;                 /* > 0: DBSCAN's radius (m)                     */
+  int32_t min_samples;         /* >= 1, the point itself counts                */
+  int32_t num_clusters;        /* C in [1, RV_SEG_MAXSLOTS]                    */
+  int32_t num_points;          /* P in [1, RV_SEG_MAX_POINTS]                  */
+  int64_t draw_index;          /* [0, 2^32): which observation of the env      */
+} rv_segment_params;
+int  rv_deproject(rv_world* w, int32_t env_first, int32_t env_count, const float* d_depth, float* d_points, uint8_t* d_valid);
+int  rv_segment_cloud(rv_world* w, const rv_segment_params* h_params, int32_t env_first, int32_t env_count,
+                      const float* d_points, const uint8_t* d_valid /* or NULL */, int32_t m,
+                      int32_t* d_labels, float* d_clouds, int32_t* d_slot_labels, int32_t* d_slot_counts,
+                      float* d_plane, int32_t* d_info);
+
 /* ---- s aimed pushes per env as proposals for look-ahead: the reference's HeuristicPushSampler.sample(position,
  *      body_mask, num_episodes, num_steps, num_samples) (heuristic_push_sampler.py:52-123) and a planning form of it.
  *      A push starts at least start_margin from every body and has its start or its end within motion_margin of its

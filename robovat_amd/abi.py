@@ -253,6 +253,34 @@ DEPTH_NOISE_API = {
 }
 
 
+RV_SEG_MAXPTS = 8192
+RV_SEG_MAX_HYPOTHESES = 1024
+RV_SEG_MAXSLOTS = 16
+RV_SEG_MAX_POINTS = 65536
+RV_SEG_INVALID, RV_SEG_PLANE, RV_SEG_SKIPPED = -3, -2, -4
+RV_SEG_INFO_WORDS = 8
+(RV_SEG_INFO_VALID, RV_SEG_INFO_PLANE, RV_SEG_INFO_SURVIVORS, RV_SEG_INFO_KEPT, RV_SEG_INFO_CLUSTERS, RV_SEG_INFO_NOISE,
+ RV_SEG_INFO_BEST_H, RV_SEG_INFO_FLAGS) = range(8)
+RV_SEG_FLAG_NO_PLANE, RV_SEG_FLAG_OVERFLOW, RV_SEG_FLAG_BOUND, RV_SEG_FLAG_FEWER = 1, 2, 4, 8
+
+
+class rv_segment_params(C.Structure):
+    _fields_ = [
+        ('num_hypotheses', i32), ('plane_thresh', f32), ('eps', f32), ('min_samples', i32), ('num_clusters', i32),
+        ('num_points', i32), ('draw_index', C.c_int64),
+    ]
+
+
+# rv_deproject: world, env_first, env_count, d_depth, d_points, d_valid; rv_segment_cloud: world, h_params, env_first,
+# env_count, d_points, d_valid, m, d_labels, d_clouds, d_slot_labels, d_slot_counts, d_plane, d_info (include/rovat.h);
+# lib.load() binds them from here
+SEGMENT_API = {
+    'rv_deproject': (C.c_int, [C.c_void_p, i32, i32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'rv_segment_cloud': (C.c_int, [C.c_void_p, C.POINTER(rv_segment_params), i32, i32, C.c_void_p, C.c_void_p, i32,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
+
 RV_HP_MAX_SAMPLES = 1024
 RV_HP_MAX_ATTEMPTS = 32768
 RV_HP_EPISODE, RV_HP_SPREAD = 0, 1

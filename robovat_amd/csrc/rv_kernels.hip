@@ -18,6 +18,8 @@
 //                   network: the forward pass keeping its activations, a workgroup per sample for the data gradients and
 //                   the convolutions' partial sums, a thread per weight for the chains over the batch, Adam per element
 //                   (rv_dev_grasp_train.h)
+//   k_deproject / k_segment_cloud   point clouds segmented without the segmask: a keyed plane fit, DBSCAN on LDS-resident
+//                   points, the largest clusters sampled; one workgroup per env (rv_dev_segment.h)
 //   k_*             small one-thread-per-env accessors behind the getters,
 //                   setters, observation, reward and policy entry points
 #include <hip/hip_runtime.h>
@@ -46,6 +48,7 @@
 #include "rv_dev_push_route.h"
 #include "rv_dev_view.h"
 #include "rv_dev_grasp_train.h"
+#include "rv_dev_segment.h"
 
 using namespace rv;
 
@@ -617,6 +620,8 @@ struct rv_world {
   // rv_render_view: [V] env indices then [V][17] camera rows, on the device and in pinned host memory (what was uploaded
   // last: an identical call skips the copy); ev_view: the last upload has left the pinned copy
   uint8_t* d_view; uint8_t* h_view; size_t view_cap, view_bytes; hipEvent_t ev_view;
+  // rv_segment_cloud: [env_count][M] rank -> point index (words; grown on demand)
+  float* d_seg_scratch; size_t seg_scratch_cap;
 };
 
 static thread_local std::string g_err;
@@ -886,6 +891,7 @@ int rv_destroy(rv_world* w) {
   if (w->d_dn_scratch) (void)hipFree(w->d_dn_scratch);
   if (w->d_route) (void)hipFree(w->d_route);
   if (w->d_view) (void)hipFree(w->d_view);
+  if (w->d_seg_scratch) (void)hipFree(w->d_seg_scratch);
   if (w->h_view) (void)hipHostFree(w->h_view);
   (void)hipEventDestroy(w->ev0); (void)hipEventDestroy(w->ev1); (void)hipEventDestroy(w->ev_state); (void)hipEventDestroy(w->ev_view);
   delete w;
@@ -1414,6 +1420,54 @@ int rv_depth_noise(rv_world* w, const rv_depth_noise_params* h_params, const flo
   HIPCHK(hipGetLastError());
   if (v4) hipLaunchKernelGGL(k_depth_noise_apply<4>, dim3((unsigned)blocks), dim3(256), 0, w->stream, a, (int)tiles_x, (int)tiles_y);
   else hipLaunchKernelGGL(k_depth_noise_apply<1>, dim3((unsigned)blocks), dim3(256), 0, w->stream, a, (int)tiles_x, (int)tiles_y);
+  HIPCHK(hipGetLastError());
+  return RV_OK;
+}
+static int seg_env_range(const rv_world* w, const char* who, int32_t env_first, int32_t env_count) {
+  if (env_first < 0 || env_count < 1 || (long long)env_first + env_count > (long long)w->n)
+    return fail(RV_ERR_VALUE, std::string(who) + ": envs env_first .. env_first + env_count - 1 must lie in [0, N) and be at least one");
+  return RV_OK;
+}
+int rv_deproject(rv_world* w, int32_t env_first, int32_t env_count, const float* d_depth, float* d_points, uint8_t* d_valid) {
+  WCHK(w);
+  NEED(d_depth, "rv_deproject"); NEED(d_points, "rv_deproject"); NEED(d_valid, "rv_deproject");
+  if (!aligned_to(d_depth, 4) || !aligned_to(d_points, 4)) return fail(RV_ERR_VALUE, "rv_deproject: the float buffers must be 4-byte aligned");
+  int rc = seg_env_range(w, "rv_deproject", env_first, env_count); if (rc != RV_OK) return rc;
+  rc = ensure_snaps(w, (size_t)w->n); if (rc != RV_OK) return rc;
+  SIMPLE_LAUNCH(k_obs_snap, w->d_envs, w->n, w->d_snaps, w->d_scene);
+  const size_t total = (size_t)env_count * w->cfg.cam_height * w->cfg.cam_width;
+  if ((total + 255) / 256 > 0x7fffffffULL) return fail(RV_ERR_VALUE, "rv_deproject: too many pixels for one launch");
+  hipLaunchKernelGGL(k_deproject, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, w->stream, w->d_snaps, (int)env_first, total,
+                     d_depth, d_points, d_valid, w->d_cfg);
+  HIPCHK(hipGetLastError());
+  return RV_OK;
+}
+int rv_segment_cloud(rv_world* w, const rv_segment_params* h_params, int32_t env_first, int32_t env_count, const float* d_points,
+                     const uint8_t* d_valid, int32_t m, int32_t* d_labels, float* d_clouds, int32_t* d_slot_labels,
+                     int32_t* d_slot_counts, float* d_plane, int32_t* d_info) {
+  WCHK(w);
+  if (!h_params) return fail(RV_ERR_VALUE, "rv_segment_cloud: null params");
+  NEED(d_points, "rv_segment_cloud"); NEED(d_labels, "rv_segment_cloud"); NEED(d_clouds, "rv_segment_cloud");
+  NEED(d_slot_labels, "rv_segment_cloud"); NEED(d_slot_counts, "rv_segment_cloud"); NEED(d_plane, "rv_segment_cloud"); NEED(d_info, "rv_segment_cloud");
+  if (!aligned_to(d_points, 4) || !aligned_to(d_labels, 4) || !aligned_to(d_clouds, 4) || !aligned_to(d_slot_labels, 4) ||
+      !aligned_to(d_slot_counts, 4) || !aligned_to(d_plane, 4) || !aligned_to(d_info, 4))
+    return fail(RV_ERR_VALUE, "rv_segment_cloud: the buffers must be 4-byte aligned");
+  const rv_segment_params& p = *h_params;
+  int rc = seg_env_range(w, "rv_segment_cloud", env_first, env_count); if (rc != RV_OK) return rc;
+  if (m < 1 || m > (1 << 24)) return fail(RV_ERR_VALUE, "rv_segment_cloud: M outside [1, 2^24]");
+  if (p.num_hypotheses < 0 || p.num_hypotheses > RV_SEG_MAX_HYPOTHESES) return fail(RV_ERR_VALUE, "rv_segment_cloud: num_hypotheses outside [0, RV_SEG_MAX_HYPOTHESES]");
+  if (p.num_clusters < 1 || p.num_clusters > RV_SEG_MAXSLOTS) return fail(RV_ERR_VALUE, "rv_segment_cloud: num_clusters outside [1, RV_SEG_MAXSLOTS]");
+  if (p.num_points < 1 || p.num_points > RV_SEG_MAX_POINTS) return fail(RV_ERR_VALUE, "rv_segment_cloud: num_points outside [1, 65536]");
+  if (!(p.eps > 0.0f) || !(p.eps - p.eps == 0.0f)) return fail(RV_ERR_VALUE, "rv_segment_cloud: eps must be positive and finite");
+  if (!(p.plane_thresh > 0.0f) || !(p.plane_thresh - p.plane_thresh == 0.0f)) return fail(RV_ERR_VALUE, "rv_segment_cloud: plane_thresh must be positive and finite");
+  if (p.min_samples < 1) return fail(RV_ERR_VALUE, "rv_segment_cloud: min_samples < 1");
+  if (p.draw_index < 0 || p.draw_index > 0xffffffffLL) return fail(RV_ERR_VALUE, "rv_segment_cloud: draw_index outside [0, 2^32)");
+  rc = ensure_floats(w, &w->d_seg_scratch, &w->seg_scratch_cap, (size_t)env_count * (size_t)m); if (rc != RV_OK) return rc;
+  SegArgs a;
+  a.p = p; a.pts = d_points; a.valid = d_valid; a.M = m; a.env_first = env_first;
+  a.labels = d_labels; a.clouds = d_clouds; a.slot_labels = d_slot_labels; a.slot_counts = d_slot_counts; a.plane = d_plane; a.info = d_info;
+  a.idx = reinterpret_cast<int32_t*>(w->d_seg_scratch);
+  hipLaunchKernelGGL(k_segment_cloud, dim3((unsigned)env_count), dim3(RV_SEG_THREADS), 0, w->stream, w->d_cfg, a);
   HIPCHK(hipGetLastError());
   return RV_OK;
 }

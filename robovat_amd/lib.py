@@ -44,6 +44,7 @@ SYMBOLS = [
     'rv_grasp_quality_train_workspace_floats', 'rv_grasp_quality_forward_train', 'rv_grasp_quality_backward', 'rv_adam_step',
     'rv_grasp_refine',
     'rv_render_view',
+    'rv_deproject', 'rv_segment_cloud',
 ]
 
 _EXC = {abi.RV_ERR_VALUE: ValueError, abi.RV_ERR_STATE: RuntimeError,
@@ -188,7 +189,8 @@ def load():
         getattr(lib, name).argtypes = [vp, vp]
     abi.bind_state_api(lib)
     for api in (abi.ANTIPODAL_API, abi.CEM_API, abi.DEPTH_NOISE_API, abi.PUSH_PROPOSAL_API, abi.PUSH_ROUTE_API,
-                abi.GRASP_CROP_API, abi.GRASP_QUALITY_API, abi.GRASP_TRAIN_API, abi.GRASP_REFINE_API, abi.VIEW_API):
+                abi.GRASP_CROP_API, abi.GRASP_QUALITY_API, abi.GRASP_TRAIN_API, abi.GRASP_REFINE_API, abi.VIEW_API,
+                abi.SEGMENT_API):
         for name, (res, args) in api.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, list(args)
@@ -299,6 +301,15 @@ def depth_noise_params(config=None, **overrides):
                                   gamma_shape=float(cfg.get('GAMMA_SHAPE', 1000.0)), prob=float(cfg.get('PROB', 0.5)),
                                   rescale_factor=int(r) if float(r) == int(r) else -1, sigma=float(cfg.get('SIGMA', 0.005)))
     return _override(p, 'depth_noise_params', overrides)
+
+
+def segment_params(num_points=256, num_clusters=abi.RV_MAXB, **overrides):
+    """An ``rv_segment_params`` with the reference's constants: 50 plane hypotheses (PCL's default iteration count, as
+    recalled), plane_thresh 0.015 (``remove_table``), eps 0.02 and min_samples 50 (``cluster(method='dbscan')``),
+    ``num_clusters`` slots of ``num_points`` points, draw_index 0.  Keyword arguments override fields by their C names."""
+    p = abi.rv_segment_params(num_hypotheses=50, plane_thresh=0.015, eps=0.02, min_samples=50, num_clusters=int(num_clusters),
+                              num_points=int(num_points), draw_index=0)
+    return _override(p, 'segment_params', overrides)
 
 
 def grasp_crop_params(crop_height=32, crop_width=32, step=3, **overrides):
@@ -715,6 +726,70 @@ class World(object):
         check(self.lib.rv_depth_noise(self.h, C.byref(p), self._ptr(d), self._ptr(out), None if g is None else self._ptr(g),
                                       None if ap is None else self._ptr(ap), None if grid is None else self._ptr(grid)))
         return (out, g, ap, grid) if record else out
+
+    # -- point clouds segmented without the segmask (include/rovat.h: rv_deproject / rv_segment_cloud)
+    def deproject(self, depth, env_first=0):
+        """rv_deproject: ``depth`` float32 [n, H, W] (the camera's size) of the envs ``env_first`` .. ``env_first + n - 1``
+        through each env's own calibration.  Returns (points float32 [n, H * W, 3], valid uint8 [n, H * W]: depth > 0 and
+        inside the config's crop)."""
+        torch = self.torch
+        h, w = int(self.cfg.cam_height), int(self.cfg.cam_width)
+        d = torch.as_tensor(depth, dtype=torch.float32, device=self.device)
+        if d.dim() != 3 or tuple(d.shape[1:]) != (h, w):
+            raise ValueError('deproject: depth must be [n, %d, %d], got %s' % (h, w, tuple(d.shape)))
+        d = d.contiguous()
+        n = int(d.shape[0])
+        pts = self._new((n, h * w, 3), torch.float32)
+        valid = self._new((n, h * w), torch.uint8)
+        check(self.lib.rv_deproject(self.h, int(env_first), n, self._ptr(d), self._ptr(pts), self._ptr(valid)))
+        return pts, valid
+
+    def segment_cloud(self, points, valid, params, env_first=0):
+        """rv_segment_cloud: ``points`` float32 [n, M, 3] and ``valid`` uint8 [n, M] (or None: all valid) of the envs
+        ``env_first`` .. ``env_first + n - 1``; ``params``: ``segment_params(...)``.  Returns a dict of device tensors:
+        clouds float32 [n, C, P, 3], labels int32 [n, M], slot_labels / slot_counts int32 [n, C], plane float32 [n, 4], info
+        int32 [n, 8] (abi.RV_SEG_INFO_*)."""
+        torch = self.torch
+        pts = torch.as_tensor(points, dtype=torch.float32, device=self.device)
+        if pts.dim() != 3 or int(pts.shape[2]) != 3:
+            raise ValueError('segment_cloud: points must be [n, M, 3], got %s' % (tuple(pts.shape),))
+        pts = pts.contiguous()
+        n, m = int(pts.shape[0]), int(pts.shape[1])
+        v = None
+        if valid is not None:
+            v = torch.as_tensor(valid, device=self.device)
+            if tuple(v.shape) != (n, m):
+                raise ValueError('segment_cloud: valid must be [n, M] = [%d, %d], got %s' % (n, m, tuple(v.shape)))
+            v = v.to(torch.uint8).contiguous()
+        c = min(max(int(params.num_clusters), 1), abi.RV_SEG_MAXSLOTS)      # (the library refuses what is outside)
+        p = min(max(int(params.num_points), 1), abi.RV_SEG_MAX_POINTS)
+        out = dict(clouds=self._new((n, c, p, 3), torch.float32), labels=self._new((n, max(m, 1)), torch.int32),
+                   slot_labels=self._new((n, c), torch.int32), slot_counts=self._new((n, c), torch.int32),
+                   plane=self._new((n, 4), torch.float32), info=self._new((n, abi.RV_SEG_INFO_WORDS), torch.int32))
+        check(self.lib.rv_segment_cloud(self.h, C.byref(params), int(env_first), n, self._ptr(pts), None if v is None else self._ptr(v),
+                                        m, self._ptr(out['labels']), self._ptr(out['clouds']), self._ptr(out['slot_labels']),
+                                        self._ptr(out['slot_counts']), self._ptr(out['plane']), self._ptr(out['info'])))
+        return out
+
+    def clustered_point_cloud(self, params, chunk=256, depth=None, labels=False):
+        """render -> deproject -> segment_cloud for every env, ``chunk`` envs at a time so that the [chunk, H * W, 3] points
+        stay bounded.  ``depth``: float32 [N, H, W] to segment instead of a fresh render (a noisy one, say).  Returns the dict
+        of ``segment_cloud`` for all N envs (``labels`` [N, H * W] only when asked for)."""
+        torch = self.torch
+        chunk = int(chunk)
+        if chunk < 1:
+            raise ValueError('clustered_point_cloud: chunk must be positive')
+        if depth is None:
+            depth, _ = self.render(segmask=False)
+        parts = []
+        for first in range(0, self.n, chunk):
+            d = depth[first:first + chunk]
+            pts, valid = self.deproject(d, env_first=first)
+            r = self.segment_cloud(pts, valid, params, env_first=first)
+            if not labels:
+                del r['labels']
+            parts.append(r)
+        return {k: torch.cat([r[k] for r in parts], dim=0) for k in parts[0]}
 
     # -- grasp-centred depth crops (include/rovat.h: rv_grasp_crops)
     def grasp_crops(self, depth, grasps, params, out=None, grasp_depths=True):

@@ -6,6 +6,7 @@ name-compatible handles for code written against the reference.
 
 * ``CameraObs(modality='rgb' | 'depth' | 'segmask')``      camera_obs.py:33-88
 * ``SegmentedPointCloudObs``                              camera_obs.py:182-238
+* ``PointCloudObs``                                       camera_obs.py:90-124
 * ``PoseObs(modality='position' | 'pose' | 'pose2d' | 'yaw_cossin')``   pose_obs.py:17-73
 """
 import numpy as np
@@ -69,18 +70,68 @@ class CameraObs(Observation):
 
 
 class SegmentedPointCloudObs(Observation):
-    """camera_obs.py:182-238: [num_bodies, num_points, 3] per env, from ``rv_observe``."""
+    """camera_obs.py:182-238: [num_bodies, num_points, 3] per env.  ``segmentation='segmask'`` (the default): grouped by
+    the renderer's segmask, from ``rv_observe`` -- the reference's branch with a simulator.  ``segmentation='cluster'``: its
+    branch on the real sensor, table plane removed and DBSCAN clusters in the slots (``rv_segment_cloud``, DESIGN.md §25;
+    the slots are then in cluster order, not body order); ``segment``: fields of ``lib.segment_params``."""
 
-    def __init__(self, camera=None, num_points=None, num_bodies=None, crop_min=None, crop_max=None, name=None, env_index=0):
+    def __init__(self, camera=None, num_points=None, num_bodies=None, crop_min=None, crop_max=None, name=None, env_index=0,
+                 segmentation='segmask', draw_index=0, **segment):
         Observation.__init__(self, name=name or 'point_cloud')
+        if segmentation not in ('segmask', 'cluster'):
+            raise ValueError('Unrecognized segmentation: %r.' % (segmentation,))
         self.env_index = int(env_index)
+        self.segmentation, self.draw_index, self.segment = segmentation, int(draw_index), dict(segment)
+        self.num_points, self.num_bodies = num_points, num_bodies
+
+    def _params(self):
+        from robovat_amd import abi, lib
+        return lib.segment_params(num_points=int(self.num_points or self.world.cfg.num_points),
+                                  num_clusters=int(self.num_bodies or abi.RV_MAXB), draw_index=self.draw_index, **self.segment)
 
     def get_gym_space(self):
         from robovat_amd import abi
+        if self.segmentation == 'cluster':
+            p = self._params()
+            return _Box(-np.inf, np.inf, (int(p.num_clusters), int(p.num_points), 3), np.float32)
         return _Box(-np.inf, np.inf, (abi.RV_MAXB, int(self.world.cfg.num_points), 3), np.float32)
 
     def get_observation(self):
+        if self.segmentation == 'cluster':
+            return _segment_one(self.world, self.env_index, self._params())['clouds'][0].cpu().numpy()
         return self.world.observe(point_cloud=True)['point_cloud'][self.env_index].cpu().numpy()
+
+
+def _segment_one(world, env_index, params):
+    """render -> deproject -> segment_cloud of one env of the world"""
+    depth, _ = world.render(segmask=False)
+    pts, valid = world.deproject(depth[env_index:env_index + 1], env_first=env_index)
+    return world.segment_cloud(pts, valid, params, env_first=env_index)
+
+
+class PointCloudObs(Observation):
+    """camera_obs.py:90-124: remove_table -> downsample, [num_points, 3].  The plane stage of ``rv_segment_cloud``, then
+    ONE slot that holds every survivor: eps is set so large (1e15 m) that all survivors are neighbours, min_samples 1.  More
+    than RV_SEG_MAXPTS survivors are thinned to that many evenly spaced ones before the draw."""
+    ALL_EPS = 1e15
+
+    def __init__(self, camera=None, num_points=None, crop_min=None, crop_max=None, name=None, env_index=0, draw_index=0,
+                 plane_thresh=0.015, num_hypotheses=50):
+        Observation.__init__(self, name=name or 'point_cloud')
+        self.env_index, self.draw_index, self.num_points = int(env_index), int(draw_index), num_points
+        self.plane_thresh, self.num_hypotheses = float(plane_thresh), int(num_hypotheses)
+
+    def _params(self):
+        from robovat_amd import lib
+        return lib.segment_params(num_points=int(self.num_points or self.world.cfg.num_points), num_clusters=1,
+                                  draw_index=self.draw_index, eps=self.ALL_EPS, min_samples=1, plane_thresh=self.plane_thresh,
+                                  num_hypotheses=self.num_hypotheses)
+
+    def get_gym_space(self):
+        return _Box(-np.inf, np.inf, (int(self._params().num_points), 3), np.float32)
+
+    def get_observation(self):
+        return _segment_one(self.world, self.env_index, self._params())['clouds'][0, 0].cpu().numpy()
 
 
 class PoseObs(Observation):

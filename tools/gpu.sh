@@ -39,6 +39,8 @@
 #                  durations from a profiler run of the step half, and their resources
 #   render_view    tools/render_view_bench.py: rv_render_view next to rv_render_rgb, supersampling in rays per second, and
 #                  record_step next to a plain step(); the kernel's resources
+#   segment        tools/segment_bench.py: rv_deproject / rv_segment_cloud on a chunk of 256 push envs against a torch
+#                  restatement of the plane scoring and the neighbour count and the host pipeline; the kernels' resources
 #   lanes          SQ_THREAD_CYCLES_VALU / SQ_ACTIVE_INST_VALU lane-utilisation pass (headline and no-deactivation)
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}; TAG=$1; shift
 O=$R/gpurun_out/$TAG; mkdir -p $O; cd $R
@@ -134,6 +136,12 @@ for STAGE in "$@"; do
       python tools/kernel_resources.py > $O/kernel_resources_all.txt 2>&1
       grep -h "^kernel\|render\|obs_snap" $O/kernel_resources_all.txt > $O/render_view_kernel_resources.txt
       tail -30 $O/render_view_bench.txt; cat $O/render_view_kernel_resources.txt ;;
+    segment)
+      timeout -k 10 600 python tools/segment_bench.py --out $O/segment_cloud_bench.txt > $O/segment_cloud_bench.log 2>&1
+      echo "segment rc=$?" >> $O/time.txt
+      python tools/kernel_resources.py > $O/kernel_resources_all.txt 2>&1
+      grep -h "^kernel\|segment_cloud\|deproject" $O/kernel_resources_all.txt > $O/segment_cloud_kernel_resources.txt
+      tail -30 $O/segment_cloud_bench.txt; cat $O/segment_cloud_kernel_resources.txt ;;
     lanes)
       cd /tmp
       for V in head nd; do
