@@ -22,6 +22,7 @@
 #ifndef ROVAT_H_
 #define ROVAT_H_
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -769,6 +770,49 @@ int  rv_segment_cloud(rv_world* w, const rv_segment_params* h_params, int32_t en
                       const float* d_points, const uint8_t* d_valid /* or NULL */, int32_t m,
                       int32_t* d_labels, float* d_clouds, int32_t* d_slot_labels, int32_t* d_slot_counts,
                       float* d_plane, int32_t* d_info);
+
+/* ---- exactly C groups of the points rv_segment_cloud clustered: the reference's second cluster() call (camera_obs.py:
+ *      208-210), scikit-learn's Ward agglomeration on the symmetrised k-nearest-neighbour graph cut at C clusters, then the
+ *      grouping of rv_segment_cloud on those groups.  The definition is written out operation for operation in
+ *      csrc/rv_dev_ward.h; the clustering is float64.  A chunk of envs like its two neighbours; reads no
+ *      env state but the global env id, changes none; asynchronous on the world's stream.
+ *      Input: d_points [env_count][M][3] and d_labels [env_count][M] as rv_segment_cloud wrote them; the points with a
+ *      label >= 0 and finite coordinates are agglomerated (at most RV_WARD_MAXPTS: more are thinned to that many evenly
+ *      spaced, the rest RV_SEG_SKIPPED in d_groups, RV_WARD_FLAG_OVERFLOW).  Outputs: d_groups [env_count][M] (the group
+ *      number, groups numbered by ascending smallest member index; a negative label is kept), d_clouds
+ *      [env_count][C][P][3] and d_slot_counts [env_count][C] (slot s = group s; fewer input points than groups: every
+ *      point its own group, the other slots empty, RV_WARD_FLAG_FEWER), d_info [env_count][RV_WARD_INFO_WORDS].  The draws
+ *      use the counter words of rv_segment_cloud's grouping, which this call replaces: where the groups are the clusters,
+ *      d_clouds is bit for bit rv_segment_cloud's.  d_workspace: rv_ward_workspace_bytes(env_count) bytes of device
+ *      memory, 8-byte aligned, contents don't matter (0 for env_count < 1).
+ *      RV_ERR_VALUE, with nothing launched: a NULL params, buffer or workspace, a workspace that is too small or not
+ *      8-byte aligned, a buffer that is not 4-byte aligned, an env range outside the world, M outside [1, 2^24],
+ *      num_neighbors outside [1, RV_WARD_MAX_NEIGHBORS], num_groups outside [1, RV_SEG_MAXSLOTS], num_points outside
+ *      [1, RV_SEG_MAX_POINTS], draw_index outside [0, 2^32). ---- */
+#define RV_WARD_MAXPTS        2048
+#define RV_WARD_MAX_NEIGHBORS 128
+#define RV_WARD_INFO_WORDS    8
+#define RV_WARD_INFO_INPUT 0        /* points with a label >= 0 and finite coordinates */
+#define RV_WARD_INFO_KEPT 1         /* of them agglomerated (<= RV_WARD_MAXPTS)        */
+#define RV_WARD_INFO_COMPONENTS 2   /* of the neighbour graph before completion        */
+#define RV_WARD_INFO_EDGES_ADDED 3  /* by the completion                               */
+#define RV_WARD_INFO_MERGES 4       /* merge steps taken                               */
+#define RV_WARD_INFO_GROUPS 5       /* groups left                                     */
+#define RV_WARD_INFO_RESERVED 6     /* 0                                               */
+#define RV_WARD_INFO_FLAGS 7
+#define RV_WARD_FLAG_OVERFLOW 2   /* more than RV_WARD_MAXPTS input points */
+#define RV_WARD_FLAG_BOUND    4   /* a step found no adjacent pair: never expected, result not to be trusted */
+#define RV_WARD_FLAG_FEWER    8   /* fewer input points than groups */
+typedef struct rv_ward_params {
+  int32_t num_neighbors;   /* k in [1, RV_WARD_MAX_NEIGHBORS]; the reference uses 100 */
+  int32_t num_groups;      /* C in [1, RV_SEG_MAXSLOTS] */
+  int32_t num_points;      /* P in [1, RV_SEG_MAX_POINTS] */
+  int64_t draw_index;      /* [0, 2^32) */
+} rv_ward_params;
+size_t rv_ward_workspace_bytes(int32_t env_count);
+int  rv_ward_groups(rv_world* w, const rv_ward_params* h_params, int32_t env_first, int32_t env_count,
+                    const float* d_points, const int32_t* d_labels, int32_t m, void* d_workspace, size_t workspace_bytes,
+                    int32_t* d_groups, float* d_clouds, int32_t* d_slot_counts, int32_t* d_info);
 
 /* ---- s aimed pushes per env as proposals for look-ahead: the reference's HeuristicPushSampler.sample(position,
  *      body_mask, num_episodes, num_steps, num_samples) (heuristic_push_sampler.py:52-123) and a planning form of it.

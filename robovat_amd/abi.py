@@ -281,6 +281,29 @@ SEGMENT_API = {
 }
 
 
+RV_WARD_MAXPTS = 2048
+RV_WARD_MAX_NEIGHBORS = 128
+RV_WARD_INFO_WORDS = 8
+(RV_WARD_INFO_INPUT, RV_WARD_INFO_KEPT, RV_WARD_INFO_COMPONENTS, RV_WARD_INFO_EDGES_ADDED, RV_WARD_INFO_MERGES,
+ RV_WARD_INFO_GROUPS, RV_WARD_INFO_RESERVED, RV_WARD_INFO_FLAGS) = range(8)
+RV_WARD_FLAG_OVERFLOW, RV_WARD_FLAG_BOUND, RV_WARD_FLAG_FEWER = 2, 4, 8
+
+
+class rv_ward_params(C.Structure):
+    _fields_ = [
+        ('num_neighbors', i32), ('num_groups', i32), ('num_points', i32), ('draw_index', C.c_int64),
+    ]
+
+
+# rv_ward_workspace_bytes: env_count; rv_ward_groups: world, h_params, env_first, env_count, d_points, d_labels, m,
+# d_workspace, workspace_bytes, d_groups, d_clouds, d_slot_counts, d_info (include/rovat.h); lib.load() binds them from here
+WARD_API = {
+    'rv_ward_workspace_bytes': (C.c_size_t, [i32]),
+    'rv_ward_groups': (C.c_int, [C.c_void_p, C.POINTER(rv_ward_params), i32, i32, C.c_void_p, C.c_void_p, i32, C.c_void_p,
+                                 C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
+
 RV_HP_MAX_SAMPLES = 1024
 RV_HP_MAX_ATTEMPTS = 32768
 RV_HP_EPISODE, RV_HP_SPREAD = 0, 1

@@ -53,9 +53,9 @@
 //   m >= P: the P members with the smallest (key, index), in that order;  0 < m < P: draw j takes the member of rank
 //   mulhi(o0, m);  m == 0: zeros.
 //   Deviation: the reference's second cluster() call (Ward agglomeration on a 100-nearest-neighbour graph, which forces
-//   exactly num_bodies groups) is not built; the C largest DBSCAN clusters stand in for it.  Where DBSCAN finds the bodies
-//   apart the two agree up to the order of the slots; where bodies touch, Ward would split the merged blob and this leaves
-//   a slot empty (RV_SEG_FLAG_FEWER).
+//   exactly num_bodies groups) is not part of this kernel: it is rv_ward_groups (rv_dev_ward.h), which takes
+//   the labels written here and replaces this grouping.  Where DBSCAN finds the bodies apart the two agree up to the order
+//   of the slots; where bodies touch, Ward splits the merged blob and this leaves a slot empty (RV_SEG_FLAG_FEWER).
 //
 // info row: RV_SEG_INFO_* of include/rovat.h.
 #pragma once

@@ -20,6 +20,9 @@
 //                   (rv_dev_grasp_train.h)
 //   k_deproject / k_segment_cloud   point clouds segmented without the segmask: a keyed plane fit, DBSCAN on LDS-resident
 //                   points, the largest clusters sampled; one workgroup per env (rv_dev_segment.h)
+//   k_ward_groups   exactly C groups of the clustered points: Ward agglomeration on the k-nearest-neighbour graph in float64,
+//                   cluster moments and cached partners in LDS, adjacency as a bit matrix in the caller's workspace; one
+//                   workgroup per env (rv_dev_ward.h)
 //   k_*             small one-thread-per-env accessors behind the getters,
 //                   setters, observation, reward and policy entry points
 #include <hip/hip_runtime.h>
@@ -49,6 +52,7 @@
 #include "rv_dev_view.h"
 #include "rv_dev_grasp_train.h"
 #include "rv_dev_segment.h"
+#include "rv_dev_ward.h"
 
 using namespace rv;
 
@@ -1468,6 +1472,35 @@ int rv_segment_cloud(rv_world* w, const rv_segment_params* h_params, int32_t env
   a.labels = d_labels; a.clouds = d_clouds; a.slot_labels = d_slot_labels; a.slot_counts = d_slot_counts; a.plane = d_plane; a.info = d_info;
   a.idx = reinterpret_cast<int32_t*>(w->d_seg_scratch);
   hipLaunchKernelGGL(k_segment_cloud, dim3((unsigned)env_count), dim3(RV_SEG_THREADS), 0, w->stream, w->d_cfg, a);
+  HIPCHK(hipGetLastError());
+  return RV_OK;
+}
+size_t rv_ward_workspace_bytes(int32_t env_count) { return env_count < 1 ? 0 : (size_t)env_count * RV_WARD_ENV_BYTES; }
+int rv_ward_groups(rv_world* w, const rv_ward_params* h_params, int32_t env_first, int32_t env_count, const float* d_points,
+                   const int32_t* d_labels, int32_t m, void* d_workspace, size_t workspace_bytes, int32_t* d_groups, float* d_clouds,
+                   int32_t* d_slot_counts, int32_t* d_info) {
+  WCHK(w);
+  if (!h_params) return fail(RV_ERR_VALUE, "rv_ward_groups: null params");
+  NEED(d_points, "rv_ward_groups"); NEED(d_labels, "rv_ward_groups"); NEED(d_workspace, "rv_ward_groups"); NEED(d_groups, "rv_ward_groups");
+  NEED(d_clouds, "rv_ward_groups"); NEED(d_slot_counts, "rv_ward_groups"); NEED(d_info, "rv_ward_groups");
+  if (!aligned_to(d_points, 4) || !aligned_to(d_labels, 4) || !aligned_to(d_groups, 4) || !aligned_to(d_clouds, 4) ||
+      !aligned_to(d_slot_counts, 4) || !aligned_to(d_info, 4))
+    return fail(RV_ERR_VALUE, "rv_ward_groups: the buffers must be 4-byte aligned");
+  if (!aligned_to(d_workspace, 8)) return fail(RV_ERR_VALUE, "rv_ward_groups: the workspace must be 8-byte aligned");
+  const rv_ward_params& p = *h_params;
+  int rc = seg_env_range(w, "rv_ward_groups", env_first, env_count); if (rc != RV_OK) return rc;
+  if (workspace_bytes < rv_ward_workspace_bytes(env_count)) return fail(RV_ERR_VALUE, "rv_ward_groups: the workspace is smaller than rv_ward_workspace_bytes(env_count)");
+  if (m < 1 || m > (1 << 24)) return fail(RV_ERR_VALUE, "rv_ward_groups: M outside [1, 2^24]");
+  if (p.num_neighbors < 1 || p.num_neighbors > RV_WARD_MAX_NEIGHBORS) return fail(RV_ERR_VALUE, "rv_ward_groups: num_neighbors outside [1, RV_WARD_MAX_NEIGHBORS]");
+  if (p.num_groups < 1 || p.num_groups > RV_SEG_MAXSLOTS) return fail(RV_ERR_VALUE, "rv_ward_groups: num_groups outside [1, RV_SEG_MAXSLOTS]");
+  if (p.num_points < 1 || p.num_points > RV_SEG_MAX_POINTS) return fail(RV_ERR_VALUE, "rv_ward_groups: num_points outside [1, 65536]");
+  if (p.draw_index < 0 || p.draw_index > 0xffffffffLL) return fail(RV_ERR_VALUE, "rv_ward_groups: draw_index outside [0, 2^32)");
+  WardArgs a;
+  a.p = p; a.pts = d_points; a.labels = d_labels; a.M = m; a.env_first = env_first;
+  a.adj = reinterpret_cast<unsigned long long*>(d_workspace);
+  a.idx = reinterpret_cast<int32_t*>(a.adj + (size_t)env_count * RV_WARD_MAXPTS * RV_WARD_ROW_WORDS);
+  a.groups = d_groups; a.clouds = d_clouds; a.slot_counts = d_slot_counts; a.info = d_info;
+  hipLaunchKernelGGL(k_ward_groups, dim3((unsigned)env_count), dim3(RV_WARD_THREADS), 0, w->stream, w->d_cfg, a);
   HIPCHK(hipGetLastError());
   return RV_OK;
 }

@@ -300,18 +300,29 @@ class VecPushEnv(object):
         p = self._route_params(0, seed, route)
         return self._plans_out(self._plan_world(int(num_samples)).plan_propose_route(self.world, p, int(num_samples), int(horizon)))
 
-    def clustered_point_cloud(self, num_points=None, draw_index=0, chunk=256, depth=None, labels=False, **overrides):
+    def clustered_point_cloud(self, num_points=None, draw_index=0, chunk=256, depth=None, labels=False, grouping='largest',
+                              num_neighbors=100, **overrides):
         """The point clouds as the reference's real-sensor branch makes them (SegmentedPointCloudObs without a simulator,
         camera_obs.py:182-211): render -> deproject -> plane removal -> DBSCAN -> the ``num_clusters`` largest clusters
         sampled to ``num_points`` points (``lib.World.clustered_point_cloud``), ``chunk`` envs at a time.
         ``num_points``: None for the config's; ``overrides``: fields of ``lib.segment_params`` (eps, min_samples,
         plane_thresh, num_hypotheses, num_clusters).  Returns a dict of device tensors: clouds float32 [N, C, P, 3] and
         the diagnostics slot_labels, slot_counts [N, C], plane [N, 4], info [N, 8] (``abi.RV_SEG_INFO_*``; flag
-        RV_SEG_FLAG_FEWER: fewer clusters than slots, e.g. bodies that touch), labels [N, H * W] when asked for."""
+        RV_SEG_FLAG_FEWER: fewer clusters than slots, e.g. bodies that touch), labels [N, H * W] when asked for.
+        ``grouping='ward'``: the reference's second ``cluster()`` call after DBSCAN -- Ward agglomeration of the clustered
+        points on their ``num_neighbors``-nearest-neighbour graph into exactly ``num_clusters`` groups (``rv_ward_groups``,
+        DESIGN.md §26): clouds and slot_counts are then those groups', ward_info [N, 8] (``abi.RV_WARD_INFO_*``) is added,
+        and groups [N, H * W] with the labels."""
         from robovat_amd import lib
+        if grouping not in ('largest', 'ward'):
+            raise ValueError('Unrecognized grouping: %r.' % (grouping,))
         p = lib.segment_params(num_points=int(self.rv_config.num_points) if num_points is None else int(num_points),
                                draw_index=int(draw_index), **overrides)
-        return self.world.clustered_point_cloud(p, chunk=chunk, depth=depth, labels=labels)
+        ward = None
+        if grouping == 'ward':
+            ward = lib.ward_params(num_points=int(p.num_points), num_groups=int(p.num_clusters), num_neighbors=int(num_neighbors),
+                                   draw_index=int(draw_index))
+        return self.world.clustered_point_cloud(p, chunk=chunk, depth=depth, labels=labels, ward=ward)
 
     def rollout(self, n_steps, auto_reset=True, record=True):
         before =self.world.env_counters().cpu().numpy()[:, [2, 4]] if (auto_reset and self._physics is not None) else None
@@ -517,7 +528,8 @@ class PushEnv(object):
         return tuple(x[0] for x in self._vec.propose_route_plans(num_samples, horizon, seed, **route))
 
     def clustered_point_cloud(self, num_points=None, draw_index=0, **overrides):
-        """``VecPushEnv.clustered_point_cloud`` for this env.  Returns the dict with the leading axis dropped."""
+        """``VecPushEnv.clustered_point_cloud`` for this env (``grouping='ward'`` and ``num_neighbors`` among the
+        overrides).  Returns the dict with the leading axis dropped."""
         return {k: v[0] for k, v in self._vec.clustered_point_cloud(num_points, draw_index, **overrides).items()}
 
     def _one(self, x):

@@ -45,6 +45,7 @@ SYMBOLS = [
     'rv_grasp_refine',
     'rv_render_view',
     'rv_deproject', 'rv_segment_cloud',
+    'rv_ward_workspace_bytes', 'rv_ward_groups',
 ]
 
 _EXC = {abi.RV_ERR_VALUE: ValueError, abi.RV_ERR_STATE: RuntimeError,
@@ -190,7 +191,7 @@ def load():
     abi.bind_state_api(lib)
     for api in (abi.ANTIPODAL_API, abi.CEM_API, abi.DEPTH_NOISE_API, abi.PUSH_PROPOSAL_API, abi.PUSH_ROUTE_API,
                 abi.GRASP_CROP_API, abi.GRASP_QUALITY_API, abi.GRASP_TRAIN_API, abi.GRASP_REFINE_API, abi.VIEW_API,
-                abi.SEGMENT_API):
+                abi.SEGMENT_API, abi.WARD_API):
         for name, (res, args) in api.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, list(args)
@@ -312,6 +313,13 @@ def segment_params(num_points=256, num_clusters=abi.RV_MAXB, **overrides):
     return _override(p, 'segment_params', overrides)
 
 
+def ward_params(num_points=256, num_groups=abi.RV_MAXB, num_neighbors=100, **overrides):
+    """An ``rv_ward_params`` with the reference's constant: the 100 nearest neighbours of its second ``cluster()`` call,
+    ``num_groups`` slots of ``num_points`` points, draw_index 0.  Keyword arguments override fields by their C names."""
+    p = abi.rv_ward_params(num_neighbors=int(num_neighbors), num_groups=int(num_groups), num_points=int(num_points), draw_index=0)
+    return _override(p, 'ward_params', overrides)
+
+
 def grasp_crop_params(crop_height=32, crop_width=32, step=3, **overrides):
     """An ``rv_grasp_crop_params``: ``crop_height`` x ``crop_width`` output pixels, every ``step``-th pixel of a window of
     ``step`` times that size around the grasp.  The defaults are BUILD-CHOSEN, not the reference's (its ``transform`` and
@@ -401,6 +409,7 @@ class World(object):
         self.device_index = int(device)
         self.device = torch.device('cuda', self.device_index)
         self.h = C.c_void_p()
+        self._ward_workspace = None      # (ward_groups: int64 words, grown on demand)
         check(self.lib.rv_create(C.byref(cfg), C.byref(scene), self.device_index, C.byref(self.h)))
         # run on torch's current stream so torch ops and kernels are ordered
         self.use_current_stream()
@@ -771,10 +780,41 @@ class World(object):
                                         self._ptr(out['slot_counts']), self._ptr(out['plane']), self._ptr(out['info'])))
         return out
 
-    def clustered_point_cloud(self, params, chunk=256, depth=None, labels=False):
+    def ward_groups(self, points, labels, params, env_first=0):
+        """rv_ward_groups: ``points`` float32 [n, M, 3] and ``labels`` int32 [n, M] (``segment_cloud``'s) of the envs
+        ``env_first`` .. ``env_first + n - 1``; ``params``: ``ward_params(...)``.  The points with a label >= 0 are
+        agglomerated into exactly C groups.  Returns a dict of device tensors: clouds float32 [n, C, P, 3],
+        groups int32 [n, M], slot_counts int32 [n, C], info int32 [n, 8] (abi.RV_WARD_INFO_*).  The workspace belongs to
+        the world: allocated on the first call, grown when a larger chunk comes."""
+        torch = self.torch
+        pts = torch.as_tensor(points, dtype=torch.float32, device=self.device)
+        if pts.dim() != 3 or int(pts.shape[2]) != 3:
+            raise ValueError('ward_groups: points must be [n, M, 3], got %s' % (tuple(pts.shape),))
+        pts = pts.contiguous()
+        n, m = int(pts.shape[0]), int(pts.shape[1])
+        lab = torch.as_tensor(labels, device=self.device)
+        if tuple(lab.shape) != (n, m):
+            raise ValueError('ward_groups: labels must be [n, M] = [%d, %d], got %s' % (n, m, tuple(lab.shape)))
+        lab = lab.to(torch.int32).contiguous()
+        c = min(max(int(params.num_groups), 1), abi.RV_SEG_MAXSLOTS)      # (the library refuses what is outside)
+        p = min(max(int(params.num_points), 1), abi.RV_SEG_MAX_POINTS)
+        need = int(self.lib.rv_ward_workspace_bytes(n))
+        ws = self._ward_workspace
+        if ws is None or ws.numel() * 8 < need:
+            ws = self._ward_workspace = torch.empty(((need + 7) // 8,), dtype=torch.int64, device=self.device)
+        out = dict(clouds=self._new((n, c, p, 3), torch.float32), groups=self._new((n, max(m, 1)), torch.int32),
+                   slot_counts=self._new((n, c), torch.int32), info=self._new((n, abi.RV_WARD_INFO_WORDS), torch.int32))
+        check(self.lib.rv_ward_groups(self.h, C.byref(params), int(env_first), n, self._ptr(pts), self._ptr(lab), m, self._ptr(ws),
+                                      ws.numel() * 8, self._ptr(out['groups']), self._ptr(out['clouds']),
+                                      self._ptr(out['slot_counts']), self._ptr(out['info'])))
+        return out
+
+    def clustered_point_cloud(self, params, chunk=256, depth=None, labels=False, ward=None):
         """render -> deproject -> segment_cloud for every env, ``chunk`` envs at a time so that the [chunk, H * W, 3] points
         stay bounded.  ``depth``: float32 [N, H, W] to segment instead of a fresh render (a noisy one, say).  Returns the dict
-        of ``segment_cloud`` for all N envs (``labels`` [N, H * W] only when asked for)."""
+        of ``segment_cloud`` for all N envs (``labels`` [N, H * W] only when asked for).  ``ward``: ``ward_params(...)`` to
+        chain ``ward_groups`` on every chunk: ``clouds`` and ``slot_counts`` are then its exactly-C groups, ``ward_info``
+        [N, 8] is added, and ``groups`` [N, H * W] next to ``labels`` when those are asked for."""
         torch = self.torch
         chunk = int(chunk)
         if chunk < 1:
@@ -786,6 +826,11 @@ class World(object):
             d = depth[first:first + chunk]
             pts, valid = self.deproject(d, env_first=first)
             r = self.segment_cloud(pts, valid, params, env_first=first)
+            if ward is not None:
+                g = self.ward_groups(pts, r['labels'], ward, env_first=first)
+                r['clouds'], r['slot_counts'], r['ward_info'] = g['clouds'], g['slot_counts'], g['info']
+                if labels:
+                    r['groups'] = g['groups']
             if not labels:
                 del r['labels']
             parts.append(r)

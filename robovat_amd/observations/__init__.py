@@ -73,13 +73,19 @@ class SegmentedPointCloudObs(Observation):
     """camera_obs.py:182-238: [num_bodies, num_points, 3] per env.  ``segmentation='segmask'`` (the default): grouped by
     the renderer's segmask, from ``rv_observe`` -- the reference's branch with a simulator.  ``segmentation='cluster'``: its
     branch on the real sensor, table plane removed and DBSCAN clusters in the slots (``rv_segment_cloud``, DESIGN.md §25;
-    the slots are then in cluster order, not body order); ``segment``: fields of ``lib.segment_params``."""
+    the slots are then in cluster order, not body order); ``segment``: fields of ``lib.segment_params``.  With
+    ``grouping='largest'`` (the default) the slots hold the largest DBSCAN clusters and bodies that touch leave one empty;
+    ``grouping='ward'`` adds the reference's second ``cluster()`` call, Ward agglomeration of the clustered points on their
+    ``num_neighbors``-nearest-neighbour graph into exactly ``num_bodies`` groups (``rv_ward_groups``)."""
 
     def __init__(self, camera=None, num_points=None, num_bodies=None, crop_min=None, crop_max=None, name=None, env_index=0,
-                 segmentation='segmask', draw_index=0, **segment):
+                 segmentation='segmask', draw_index=0, grouping='largest', num_neighbors=100, **segment):
         Observation.__init__(self, name=name or 'point_cloud')
         if segmentation not in ('segmask', 'cluster'):
             raise ValueError('Unrecognized segmentation: %r.' % (segmentation,))
+        if grouping not in ('largest', 'ward'):
+            raise ValueError('Unrecognized grouping: %r.' % (grouping,))
+        self.grouping, self.num_neighbors = grouping, int(num_neighbors)
         self.env_index = int(env_index)
         self.segmentation, self.draw_index, self.segment = segmentation, int(draw_index), dict(segment)
         self.num_points, self.num_bodies = num_points, num_bodies
@@ -98,15 +104,24 @@ class SegmentedPointCloudObs(Observation):
 
     def get_observation(self):
         if self.segmentation == 'cluster':
-            return _segment_one(self.world, self.env_index, self._params())['clouds'][0].cpu().numpy()
+            p = self._params()
+            ward = None
+            if self.grouping == 'ward':
+                from robovat_amd import lib
+                ward = lib.ward_params(num_points=int(p.num_points), num_groups=int(p.num_clusters), num_neighbors=self.num_neighbors,
+                                       draw_index=self.draw_index)
+            return _segment_one(self.world, self.env_index, p, ward)['clouds'][0].cpu().numpy()
         return self.world.observe(point_cloud=True)['point_cloud'][self.env_index].cpu().numpy()
 
 
-def _segment_one(world, env_index, params):
-    """render -> deproject -> segment_cloud of one env of the world"""
+def _segment_one(world, env_index, params, ward=None):
+    """render -> deproject -> segment_cloud (-> ward_groups, with ``ward`` params) of one env of the world"""
     depth, _ = world.render(segmask=False)
     pts, valid = world.deproject(depth[env_index:env_index + 1], env_first=env_index)
-    return world.segment_cloud(pts, valid, params, env_first=env_index)
+    r = world.segment_cloud(pts, valid, params, env_first=env_index)
+    if ward is not None:
+        r = dict(r, **world.ward_groups(pts, r['labels'], ward, env_first=env_index))
+    return r
 
 
 class PointCloudObs(Observation):

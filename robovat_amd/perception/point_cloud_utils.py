@@ -154,3 +154,108 @@ def cluster(point_cloud, num_clusters, method='agg'):
         conn = 0.5 * (conn + conn.T)
         return AgglomerativeClustering(linkage='ward', n_clusters=num_clusters, connectivity=conn).fit(pts).labels_.astype(np.int64)
     raise ValueError('Unrecognized method: %r.' % (method,))
+
+
+# ---- the second cluster() call of that branch: the definition of rv_ward_groups' clustering (csrc/rv_dev_ward.h,
+# DESIGN.md §26) in NumPy, float64, without scikit-learn; the batched version is ``lib.World.ward_groups``.
+
+def _ward_dist(mean, cnt, a, b):
+    """compute_ward_dist of scikit-learn between cluster a and the clusters b (an index array)"""
+    nn = (cnt[a] * cnt[b]) / (cnt[a] + cnt[b])
+    t = mean[a][None, :] - mean[b]
+    return ((t[:, 0] * t[:, 0] + t[:, 1] * t[:, 1]) + t[:, 2] * t[:, 2]) * nn
+
+
+def ward_graph(points, n_neighbors=100):
+    """The connectivity of ``ward_labels``: (adjacency bool [n, n], squared distances float64 [n, n], number of components
+    before completion).  Point i is joined to its min(k, n - 1) nearest points, smallest (d2, j) first, the graph is
+    symmetrised, and for every pair of components a > b (numbered by smallest member) the pair (p in a, q in b) smallest in
+    (d2, p, q) is joined too (scikit-learn's ``_fix_connected_components``)."""
+    p = np.asarray(points, np.float32).astype(np.float64).reshape(-1, 3)
+    n = len(p)
+    dx, dy, dz = [p[:, None, c] - p[None, :, c] for c in range(3)]
+    d2 = (dx * dx + dy * dy) + dz * dz
+    adj = np.zeros((n, n), bool)
+    keff = min(int(n_neighbors), n - 1)
+    if keff > 0:
+        dd = d2.copy()
+        np.fill_diagonal(dd, np.inf)
+        near = np.argsort(dd, axis=1, kind='stable')[:, :keff]
+        adj[np.arange(n)[:, None], near] = True
+        adj |= adj.T
+    comp = np.full(n, -1, np.int64)
+    ncomp = 0
+    for i in range(n):      # (ascending: a new component starts at its smallest member)
+        if comp[i] >= 0:
+            continue
+        comp[i] = ncomp
+        front = np.array([i])
+        while len(front):
+            new = np.flatnonzero(adj[front].any(axis=0) & (comp < 0))
+            comp[new] = ncomp
+            front = new
+        ncomp += 1
+    members = [np.flatnonzero(comp == c) for c in range(ncomp)]
+    for a in range(ncomp):
+        for b in range(a):
+            block = d2[np.ix_(members[a], members[b])]
+            ia, ib = np.unravel_index(np.argmin(block), block.shape)      # (the first minimum in row-major order)
+            adj[members[a][ia], members[b][ib]] = adj[members[b][ib], members[a][ia]] = True
+    return adj, d2, ncomp
+
+
+def ward_labels(point_cloud, num_clusters, n_neighbors=100):
+    """Integer labels [n]: Ward agglomeration on the symmetrised ``n_neighbors``-nearest-neighbour graph into exactly
+    ``num_clusters`` groups, as scikit-learn's ``AgglomerativeClustering(linkage='ward', connectivity=...)`` computes it and
+    as ``rv_ward_groups`` does on the device (which keeps at most 2048 points; here every point is used).  Cluster r
+    starts as point r with id r; while more than ``num_clusters`` live, the adjacent live pair smallest in (w, larger id,
+    smaller id) merges into id n + step, w = |mean_a - mean_b|^2 c_a c_b / (c_a + c_b) in float64.  The groups are numbered
+    by ascending smallest member; with fewer points than groups every point is its own group."""
+    p = np.asarray(point_cloud, np.float32).astype(np.float64).reshape(-1, 3)
+    n, c = len(p), int(num_clusters)
+    if n <= c:
+        return np.arange(n, dtype=np.int64)
+    adj, _, _ = ward_graph(p, n_neighbors)
+    mean, total, cnt, cid = p.copy(), p.copy(), np.ones(n), np.arange(n)
+    live = np.ones(n, bool)
+    owner = np.arange(n)                      # the slot of every point's cluster; a cluster lives in its smallest member's slot
+    best_w, best = np.full(n, np.inf), np.full(n, -1, np.int64)
+
+    def scan(t):
+        nb = np.flatnonzero(adj[t])
+        if not len(nb):
+            return np.inf, -1
+        w = _ward_dist(mean, cnt, t, nb)
+        o = np.lexsort((np.minimum(cid[t], cid[nb]), np.maximum(cid[t], cid[nb]), w))[0]
+        return w[o], nb[o]
+
+    for t in range(n):
+        best_w[t], best[t] = scan(t)
+    for step in range(n - c):
+        cand = np.flatnonzero(live & (best >= 0))
+        if not len(cand):
+            raise RuntimeError('ward_labels: no adjacent pair left (the graph is not connected)')
+        ids, pid = cid[cand], cid[best[cand]]
+        who = cand[np.lexsort((cand, np.minimum(ids, pid), np.maximum(ids, pid), best_w[cand]))[0]]
+        keep, dead = sorted((int(who), int(best[who])))
+        adj[keep] |= adj[dead]
+        adj[keep, [keep, dead]] = False
+        nb = np.flatnonzero(adj[keep])
+        adj[nb, dead], adj[nb, keep], adj[dead] = False, True, False
+        total[keep] = total[keep] + total[dead]
+        cnt[keep] = cnt[keep] + cnt[dead]
+        mean[keep] = total[keep] / cnt[keep]
+        cid[keep], live[dead] = n + step, False
+        owner[owner == dead] = keep
+        best_w[keep], best[keep] = np.inf, -1
+        if len(nb):
+            w = _ward_dist(mean, cnt, keep, nb)
+            o = np.lexsort((cid[nb], w))[0]
+            best_w[keep], best[keep] = w[o], nb[o]
+            gone = (best[nb] == keep) | (best[nb] == dead)
+            better = ~gone & (w < best_w[nb])      # (equal w: the older pair has the smaller ids)
+            best_w[nb[better]], best[nb[better]] = w[better], keep
+            for t in nb[gone]:
+                best_w[t], best[t] = scan(t)
+    number = np.cumsum(live) - 1
+    return number[owner].astype(np.int64)

@@ -41,6 +41,9 @@
 #                  record_step next to a plain step(); the kernel's resources
 #   segment        tools/segment_bench.py: rv_deproject / rv_segment_cloud on a chunk of 256 push envs against a torch
 #                  restatement of the plane scoring and the neighbour count and the host pipeline; the kernels' resources
+#   ward           tools/ward_bench.py: rv_ward_groups on a chunk of 256 push envs next to rv_segment_cloud, the host mirror and
+#                  scikit-learn, and what Ward does on the env-steps of a heuristic rollout where bodies touch; the kernel's
+#                  resources
 #   lanes          SQ_THREAD_CYCLES_VALU / SQ_ACTIVE_INST_VALU lane-utilisation pass (headline and no-deactivation)
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}; TAG=$1; shift
 O=$R/gpurun_out/$TAG; mkdir -p $O; cd $R
@@ -142,6 +145,12 @@ for STAGE in "$@"; do
       python tools/kernel_resources.py > $O/kernel_resources_all.txt 2>&1
       grep -h "^kernel\|segment_cloud\|deproject" $O/kernel_resources_all.txt > $O/segment_cloud_kernel_resources.txt
       tail -30 $O/segment_cloud_bench.txt; cat $O/segment_cloud_kernel_resources.txt ;;
+    ward)
+      timeout -k 10 600 python tools/ward_bench.py --out $O/ward_groups_bench.txt > $O/ward_groups_bench.log 2>&1
+      echo "ward rc=$?" >> $O/time.txt
+      python tools/kernel_resources.py > $O/kernel_resources_all.txt 2>&1
+      grep -h "^kernel\|ward_groups" $O/kernel_resources_all.txt > $O/ward_groups_kernel_resources.txt
+      tail -30 $O/ward_groups_bench.txt; cat $O/ward_groups_kernel_resources.txt ;;
     lanes)
       cd /tmp
       for V in head nd; do
