@@ -1072,6 +1072,13 @@ typedef struct rv_rollout_extra {
 int  rv_rollout_record_full(rv_world* w, int32_t n_steps, int32_t first_macro_index, int32_t auto_reset,
                             float* d_rewards, uint8_t* d_dones, const rv_obs_buffers* step_obs,
                             const rv_rollout_extra* extra);
+/* Who rendered the point clouds of the last rv_rollout_record / rv_rollout_record_full of this world (for tests).  In the
+ * plain launch of the one-wave-per-SIMD build, workgroups whose env has finished render the clouds of snapshot rows that
+ * are stored already; the rows they leave are rendered after the kernel.  by_tail + by_residual = n_steps x N (0 and 0
+ * when that call took no point clouds); by_tail = 0 on the other build, through the task queues, and with RV_PC_TAIL=0
+ * in the environment (read per launch).  RV_PC_TAIL_CAP=n: a finished workgroup renders n rows at most.  The clouds
+ * are the same bytes whoever renders them.  Synchronises the world's stream; h_ pointers are host memory. */
+int  rv_last_tail_renders(rv_world* w, int32_t* h_by_tail, int32_t* h_by_residual);
 
 /* ---- CameraObs 'depth' / 'segmask' (camera_obs.py:33-88; BulletCamera._frames,
  *      bullet_camera.py:188-235) of the simulated depth camera: eye-space depth (0 where

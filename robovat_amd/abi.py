@@ -467,6 +467,12 @@ VIEW_API = {
                                  C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
+# rv_last_tail_renders (include/rovat.h): world, h_by_tail, h_by_residual -- who rendered the point clouds of the last
+# recorded rollout (the rollout kernel's finished workgroups / the launch after it); lib.load() binds it from here
+PC_TAIL_API = {
+    'rv_last_tail_renders': (C.c_int, [C.c_void_p, C.POINTER(i32), C.POINTER(i32)]),
+}
+
 
 def bind_state_api(handle):
     """restype / argtypes of the STATE_API functions on a loaded librovat_hip.so"""

@@ -5796,6 +5796,10 @@ struct ProgArgs {
   // ROLLOUT as one task of a queue (rv_env_kernel.h): this call takes the steps k0 .. k_stop - 1 of the env's n_steps
   // (k_stop = 0: all of them, from k0 = 0 -- a plain launch); the per-launch counters are zeroed by the task that starts at 0
   int k0, k_stop;
+  // ROLLOUT, plain launch of the register-rich build (rv_env_kernel.h, "the tail"): where the env says how many of its
+  // snapshot rows are stored ([n_envs] words) -- finished workgroups of its XCD render their point clouds meanwhile.
+  // The byte offset of that pointer among the kernel's arguments (rv_kernarg_at); -1: this kernel has no tail
+  int pc_done_off;
 };
 // returns (RV_PROG_PARTIAL) 1 when the env.step() completed in this launch
 // The segments of the env program as functions of their own (RV_SEGMENTS_NOINLINE: the two-waves-per-SIMD build).  Under
@@ -5993,6 +5997,19 @@ RV_DEV int env_program(Shared& S, const Consts& K, const int prog, const ProgArg
         RV_LANES_BEGIN
           if (lane == 0 && A.budget == nullptr) rollout_record(A.rec, &S.e, (size_t)k * A.n_envs + A.env, c, K.arm);
         RV_LANES_END
+#if RV_ON_DEVICE
+        if (A.pc_done_off >= 0) {
+          // the snapshot row of step k is stored (by lane 0: the wave's counter covers it) and acknowledged by the L2 of
+          // this XCD; then the env says so -- the hand-over of the task queues (rv_env_kernel.h).  One store per env-step
+          // (the word's address and the XCD's tag are made HERE, from the launch argument and the hardware register:
+          // nothing of this lives in a register across the substep loop)
+          int* const pc_done = rv_kernarg_at<int*>(A.pc_done_off);
+          if (pc_done != nullptr) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            if (threadIdx.x == 0) __hip_atomic_store(pc_done + A.env, ((rv_xcc_id() + 1) << 24) | (k + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          }
+        }
+#endif
         RV_PROF(23)
         k_end = k + 1;
         ++k;

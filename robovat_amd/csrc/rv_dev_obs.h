@@ -17,11 +17,13 @@
 // key order; a body with more than RV_PC_MAXPIX visible pixels keeps every stride-th one, or
 // RV_PC_MAXPIX evenly spaced ones where the stride would leave fewer than num_points) or
 // num_points draws with replacement.  The observation is a pure function of a small pose
-// snapshot (ObsSnap), so a rollout records one snapshot per env.step() and all clouds of
-// the launch are rendered together afterwards.
+// snapshot (ObsSnap), so a rollout records one snapshot per env.step() and the clouds are
+// rendered from the snapshots: by finished workgroups of the rollout kernel while it still
+// runs (rv_env_kernel.h, rv_pc_tail), the rest together after it.
 #pragma once
 #include "../../include/rovat.h"
 #include "rv_dev_math.h"
+#include "rv_dev_wave.h"
 
 namespace rv {
 
@@ -205,5 +207,171 @@ RV_DEV uint32_t pc_hash(const rv_config* c, uint32_t gid, uint32_t rng_arg, uint
 }
 #define RV_PC_KEY_CTR(b, i)  (0x80000000u | ((uint32_t)(b) << 16) | (uint32_t)(i))
 #define RV_PC_DRAW_CTR(b, j) (((uint32_t)(b) << 16) | (uint32_t)(j))
+
+#if RV_ON_DEVICE
+// The cloud of body b of one observation, by ONE wave64: `o` takes its num_points x 3 floats, gid is the global env id
+// of the observation (the sampling stream).  s_pix / s_dep / s_key: RV_PC_MAXPIX words of LDS each, s_rot: RV_MAXB x 9 --
+// the caller's (k_point_cloud declares them; a finished workgroup of the rollout kernel lends its env block,
+// rv_env_kernel.h).  Every lane of the wave calls it; whoever calls it, the bytes are the same.
+RV_DEV void point_cloud_render(const ObsSnap& s, const int b, float* o, const uint32_t gid, const rv_config* c, const rv_scene* scene,
+                               uint32_t* s_pix, float* s_dep, uint32_t* s_key, float (*s_rot)[9]) {
+  const int lane = (int)threadIdx.x;
+  const int P = c->num_points;
+  if (lane < RV_MAXB) { m3 m = qmat(ldq(s.pose[lane] + 3)); stm(s_rot[lane], m); }
+  __syncthreads();
+  int n = 0;
+  const v3 cam_o = cam_position(&s);
+  if (s.shape[b] >= 0 && !s.is_static[b]) {
+    // screen rectangle of the body
+    const rv_shape* sh = &scene->shapes[s.shape[b]];
+    float mu = 1e30f, xu = -1e30f, mv = 1e30f, xv = -1e30f, mz = 1e30f;
+    {
+      const int h = lane >> 4, i = lane & 15;
+      if (h < sh->n_hulls && i < sh->n_verts[h]) {
+        const float sc = s.scale[b];
+        v3 pw = add(ld3(s.pose[b]), mulv(s_rot[b], mk(sh->verts[h][i][0] * sc, sh->verts[h][i][1] * sc, sh->verts[h][i][2] * sc)));
+        float u, v, z;
+        project_vertex(&s, pw, &u, &v, &z);
+        mz = z;
+        if (z > c->cam_near) { mu = xu = u; mv = xv = v; }
+      }
+    }
+    mu = wave_min(mu); xu = wave_max(xu); mv = wave_min(mv); xv = wave_max(xv); mz = wave_min(mz);
+    if (mz > c->cam_near) {
+      const float W1 = (float)(c->cam_width - 1), H1 = (float)(c->cam_height - 1);
+      const int u0 = (int)fclampr(ffloorr(mu) - 1.0f, 0.0f, W1), u1 = (int)fclampr(ffloorr(xu) + 2.0f, 0.0f, W1);
+      const int v0 = (int)fclampr(ffloorr(mv) - 1.0f, 0.0f, H1), v1 = (int)fclampr(ffloorr(xv) + 2.0f, 0.0f, H1);
+      const int w = u1 - u0 + 1, hh = v1 - v0 + 1;
+      const int total = (xu < 0.0f || xv < 0.0f || mu > W1 || mv > H1) ? 0 : w * hh;
+      // which link boxes of the arm can cover a pixel of this rectangle at all?  (bounding sphere of the box
+      // projected as a disc, generously; the arm is off-stage when the envs observe, so the answer is
+      // almost always "none" and the pixels pay nothing for it)
+      unsigned arm_mask = 0u;
+      if (s.arm_on == 1) {
+        bool may = false;
+        if (lane < RV_NCOL) {
+          const rv_arm* arm = &scene->arm;
+          const float hx = arm->col_half[lane][0] + c->margin, hy = arm->col_half[lane][1] + c->margin, hz = arm->col_half[lane][2] + c->margin;
+          const float r = fsqrtr(hx * hx + hy * hy + hz * hz) * 1.01f + 1e-4f;
+          float uc, vc, zc;
+          project_vertex(&s, ld3(s.arm_c[lane]), &uc, &vc, &zc);
+          if (zc - r <= c->cam_near) may = zc + r > 0.0f;          // too close to bound its disc: keep it
+          else {
+            const float f = fmaxr(fabsr(s.cam_intrinsics[0]), fabsr(s.cam_intrinsics[1])) + fabsr(s.cam_intrinsics[4]);     // (this env's calibration: camera noise)
+            const float rp = r * f / (zc - r) * 1.05f + 2.0f;
+            may = !(uc + rp < (float)u0 || uc - rp > (float)u1 || vc + rp < (float)v0 || vc - rp > (float)v1);
+          }
+        }
+        arm_mask = (unsigned)(__ballot(may) & 0x3ffull);
+      }
+      // pass 0 keeps every visible pixel; a body with more than RV_PC_MAXPIX of them is cast again and `num` of every
+      // `den` visible pixels are kept, evenly spaced in scan order (rank r goes to slot r * num / den, the first rank of
+      // a slot stays), so that the sample covers the whole body: every stride-th pixel, or, where that would leave
+      // fewer pixels than num_points asks for (they are between RV_PC_MAXPIX / 2 and RV_PC_MAXPIX), RV_PC_MAXPIX of all
+      unsigned num = 1u, den = 1u; int kept = 0;
+      for (int pass = 0; pass < 2; ++pass) {
+        n = 0;
+        for (int base = 0; base < total; base += 64) {
+          const int idx = base + lane;
+          bool vis = false; float dep = 0.0f; int u = 0, v = 0;
+          if (idx < total) {
+            u = u0 + idx % w; v = v0 + idx / w;
+            v3 dw = cam_to_world_dir(&s, pixel_dir_cam(&s, (float)u, (float)v));
+            int who = render_pixel(c, scene, s, s_rot, cam_o, dw, &dep, nullptr, arm_mask);
+            vis = (who == b) && dep > c->cam_near && crop_ok(c, deproject(&s, cam_o, (float)u, (float)v, dep));
+          }
+          const unsigned long long bal = __ballot(vis);
+          const int rank = n + (int)__popcll(bal & ((1ull << lane) - 1ull));
+          int pos = rank; bool keep = true;
+          if (den > 1u) {
+            const unsigned long long rn = (unsigned long long)rank * num;
+            pos = (int)(rn / den);
+            keep = rn - (unsigned long long)pos * den < (unsigned long long)num;
+          }
+          if (vis && keep && pos < RV_PC_MAXPIX) { s_pix[pos] = ((uint32_t)v << 16) | (uint32_t)u; s_dep[pos] = dep; }
+          n += (int)__popcll(bal);
+        }
+        if (n <= RV_PC_MAXPIX) break;
+        if (pass == 0) {
+          const int stride = (n + RV_PC_MAXPIX - 1) / RV_PC_MAXPIX;
+          kept = (n + stride - 1) / stride;
+          if (kept >= P) den = (unsigned)stride;
+          else { num = (unsigned)RV_PC_MAXPIX; den = (unsigned)n; kept = RV_PC_MAXPIX; }
+        }
+      }
+      if (den > 1u) n = kept;
+    }
+  }
+  __syncthreads();
+  if (n == 0) {                                  // group_by_labels: zeros when the body has no pixel
+    for (int j = lane; j < P * 3; j += 64) o[j] = 0.0f;
+    return;
+  }
+  if (n < P) {                                   // downsample: with replacement iff fewer than num_points
+    for (int j = lane; j < P; j += 64) {
+      const uint32_t i = pc_hash(c, gid, s.rng_arg, RV_PC_DRAW_CTR(b, j)) % (uint32_t)n;
+      const uint32_t px = s_pix[i];
+      st3(o + 3 * j, deproject(&s, cam_o, (float)(px & 0xffffu), (float)(px >> 16), s_dep[i]));
+    }
+    return;
+  }
+  // uniformly random P-subset: the P smallest keys.  Radix select of the P-th smallest key T
+  for (int i = lane; i < n; i += 64) s_key[i] = pc_hash(c, gid, s.rng_arg, RV_PC_KEY_CTR(b, i));
+  __syncthreads();
+  uint32_t prefix = 0u, mask = 0u; int k = P;
+  for (int bit = 31; bit >= 0; --bit) {
+    const uint32_t m2 = mask | (1u << bit);
+    int cnt = 0;
+    for (int base = 0; base < n; base += 64) {
+      const int i = base + lane;
+      const bool z = i < n && (s_key[i] & m2) == prefix;     // high bits match and this bit is 0
+      cnt += (int)__popcll(__ballot(z));
+    }
+    if (k > cnt) { k -= cnt; prefix |= (1u << bit); }
+    mask = m2;
+  }
+  const uint32_t T = prefix;       // k = how many keys equal to T are still needed (scan order)
+  // the selected pixels are compacted IN PLACE to the front of the three arrays (a lane writes at or below its own
+  // index, after every lane of the chunk has read its element) ...
+  int outn = 0, ties = 0;
+  for (int base = 0; base < n; base += 64) {
+    const int i = base + lane;
+    const uint32_t key = i < n ? s_key[i] : 0xffffffffu;
+    const uint32_t px = i < n ? s_pix[i] : 0u;
+    const float dp = i < n ? s_dep[i] : 0.0f;
+    const bool lt = i < n && key < T;
+    const bool eq = i < n && key == T;
+    const unsigned long long beq = __ballot(eq);
+    const int tie_rank = ties + (int)__popcll(beq & ((1ull << lane) - 1ull));
+    const bool sel = lt || (eq && tie_rank < k);
+    const unsigned long long bs = __ballot(sel);
+    const int pos = outn + (int)__popcll(bs & ((1ull << lane) - 1ull));
+    if (sel && pos < P) { s_key[pos] = key; s_pix[pos] = px; s_dep[pos] = dp; }
+    outn += (int)__popcll(bs); ties += (int)__popcll(beq);
+  }
+  __syncthreads();
+  // ... and go out in the order of their keys (ties in scan order): np.random.choice(replace=False) returns the
+  // subset in random order (point_cloud_utils.py:23-39).  Rank of an element = how many selected ones precede it;
+  // a lane ranks up to four elements per pass over the keys
+  for (int j0 = 0; j0 < P; j0 += 256) {
+    uint32_t kq[4]; int rq[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) { const int jj = j0 + lane + 64 * q; kq[q] = jj < P ? s_key[jj] : 0u; rq[q] = 0; }
+    for (int t = 0; t < P; ++t) {
+      const uint32_t kt = s_key[t];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) rq[q] += (kt < kq[q] || (kt == kq[q] && t < j0 + lane + 64 * q)) ? 1 : 0;
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int jj = j0 + lane + 64 * q;
+      if (jj < P) {
+        const uint32_t px = s_pix[jj];
+        st3(o + 3 * rq[q], deproject(&s, cam_o, (float)(px & 0xffffu), (float)(px >> 16), s_dep[jj]));
+      }
+    }
+  }
+}
+#endif
 
 }  // namespace rv

@@ -89,6 +89,23 @@ template <int N> RV_DEV float row_ror_add(float x) {
   float o = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x120 + N, 0xf, 0xf, false));
   return o + x;
 }
+// ---- where the wave runs ----
+// which XCD (0 .. 7), read from the hardware: a fact about where the wave is, not an assumption about dispatch
+RV_DEV int rv_xcc_id() {
+  unsigned x;
+  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(x));
+  return (int)(x & 7u);
+}
+// ---- a launch argument, read where it is used ----
+// The value at byte `off` of the kernel's argument segment.  The segment's address passes through an empty asm first, so
+// the load stays HERE: an argument that only the end of a long kernel wants is otherwise loaded at its entry and kept --
+// in the env kernel that is one more register spilled around the substep loop per argument
+template <typename T> RV_DEV T rv_kernarg_at(int off) {
+  typedef const char __attribute__((address_space(4))) kbyte;
+  kbyte* p = (kbyte*)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(p));
+  return *(const T __attribute__((address_space(4)))*)(p + off);
+}
 // ---- over the whole wave ----
 RV_DEV float wave_min(float x) { for (int o = 32; o > 0; o >>= 1) { float y = __shfl_xor(x, o); x = y < x ? y : x; } return x; }
 RV_DEV float wave_max(float x) { for (int o = 32; o > 0; o >>= 1) { float y = __shfl_xor(x, o); x = y > x ? y : x; } return x; }

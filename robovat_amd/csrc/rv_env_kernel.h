@@ -17,6 +17,9 @@ using namespace rv;
 
 #ifndef RV_ENV_OCCUPANCY_ATTR      // rv_kernels_occ2.hip sets it to its two-waves-per-SIMD attribute; no cap otherwise
 #define RV_ENV_OCCUPANCY_ATTR
+#define RV_ENV_PC_TAIL 1           // the register-rich build: k_env<MODE_ROLLOUT> renders point clouds in its tail (below)
+#else
+#define RV_ENV_PC_TAIL 0
 #endif
 
 // control words of the task queues (ints; every counter on a 128-byte line of its own)
@@ -26,12 +29,7 @@ enum { RV_Q_NQ = 8, RV_Q_TAKEN = 0, RV_Q_ERR = 64, RV_Q_CTL_WORDS = 96 + 96 * RV
 #define RV_Q_HEAD(x) (96 + 96 * (x))
 #define RV_Q_TAIL(x) (96 + 96 * (x) + 32)
 #define RV_Q_FRESH(x) (96 + 96 * (x) + 64)      // first steps handed out of the envs x, x + RV_Q_NQ, x + 2 RV_Q_NQ, ...
-// which XCD this wave runs on (0 .. 7)
-__device__ __forceinline__ int rv_xcc_id() {
-  unsigned x;
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(x));
-  return (int)(x & (unsigned)(RV_Q_NQ - 1));
-}
+static_assert(RV_Q_NQ == 8, "one queue per XCD: rv_xcc_id() (rv_dev_wave.h) is 0 .. 7");
 
 enum { MODE_RESET = 0, MODE_MACRO = 1, MODE_SUB = 2, MODE_WAIT = 3, MODE_ROLLOUT = 4, MODE_PARTIAL = 5 };
 
@@ -65,7 +63,111 @@ struct EnvKernelArgs {
   int q_sticky;                  // 1: a workgroup keeps an env whose step was a slow one (k_env)
   int q_wt;                      // 1: the block goes out write-through and comes in past the L1 (16-byte sc1 stores / loads): it does not occupy the L2
   int poison_lo, poison_hi;      // RV_POISON_LDS builds: the words of the scratch block that start as garbage (RV_POISON_LO / _HI: bisecting)
+  // MODE_ROLLOUT that records snapshots (rec.snaps), plain launch of the register-rich build: "the tail" (rv_pc_tail).
+  // pc_done / pc_claimed: [n_envs] words, pc_rendered: [n_substeps x n_envs] bytes, pc_count: rows the tail rendered --
+  // all zero at launch; pc_out: the point clouds; pc_cap: rows one workgroup may render.  pc_done = nullptr: no tail
+  int* pc_done; int* pc_claimed; uint8_t* pc_rendered; int* pc_count; float* pc_out; int pc_cap;
 };
+
+#if RV_ENV_PC_TAIL
+// ---- the tail: point clouds rendered by the workgroups of a recorded rollout that have finished their env.
+//
+// One env occupies one SIMD and the launch lasts as long as its slowest env; the mean env is busy about half of that, and the
+// clouds of the launch's snapshot rows (one wave per row and body, rv_dev_obs.h) used to wait for the kernel to end.  Now a
+// workgroup that has stored its env back renders rows that are there already.  It lends the renderer its LDS block (the env
+// is gone from it) plus the key array declared here -- an allocation of k_env<MODE_ROLLOUT> of this build alone.
+//
+// Protocol -- the hand-over of the task queues (k_env, below), within ONE XCD.  An env's workgroup stores the snapshot row
+// of step k (plain stores, they land in the L2 of its XCD), waits for them (asm s_waitcnt vmcnt(0)) and lane 0 stores
+// done[env] = tag | (k + 1), relaxed, agent scope; tag = the XCD it runs on + 1, read from the hardware, in the top byte.
+// A renderer looks at the envs env + 8 i (blocks are dealt round-robin over the XCDs: those are the likely neighbours --
+// for speed only) and serves env j only where the tag of done[j] is its own: same L2, whatever the dispatch did.  (A word
+// that a reader on ANOTHER XCD sees, stale or fresh, is 0 or carries another tag: never served from there.)  It claims
+// step c = claimed[j] with a compare-and-swap c -> c + 1, only while c < the done[j] it read; then ONE agent-scope acquire
+// fence + wait (drops the L1 lines of this CU), plain loads of the row, RV_MAXB clouds, rendered[row] = 1.
+// It NEVER WAITS: no poll, no sleep.  Every look at the candidates either claims a row, or sees one go to another renderer
+// -- the launch has n_steps x n_envs of them -- or ends the wave.  Rows nobody claimed (an env of another tag, a row
+// published after the last look, the last envs' rows: RV_PC_TAIL_LEAVE, pc_cap) keep rendered = 0 and are rendered by the k_point_cloud launch that follows, as all of them used to be:
+// correctness does not depend on who was how fast.  The bytes are those of k_point_cloud: one function renders both.
+template <typename T> __device__ __forceinline__ T* rv_uni_ptr(T* p) {      // (a function argument arrives in vector registers)
+  const unsigned long long v = (unsigned long long)p;
+  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
+  return (T*)(((unsigned long long)hi << 32) | (unsigned long long)lo);
+}
+// ... and as a pointer into GLOBAL memory: the words the workgroups share are read and written with global_ instructions
+#define RV_GLOBAL __attribute__((address_space(1)))
+template <typename T> __device__ __forceinline__ RV_GLOBAL T* rv_uni_gptr(T* p) { return (RV_GLOBAL T*)(unsigned long long)rv_uni_ptr(p); }
+// When does a finished workgroup stop rendering although rows are there?  When fewer than this many envs of its XCD are
+// still running (and fewer than an eighth of them: a small world keeps its tail).  One wave renders a row in half a
+// millisecond; the launch after the kernel renders what the last few envs leave -- some hundred rows -- in a fraction of
+// that, all CUs at once.  So the workgroups that leave last, the slowest env's first of all, leave at once and the kernel
+// ends with its slowest env, not some rows later.  (A look at words other workgroups write, nothing waits for them.)
+#define RV_PC_TAIL_LEAVE 4
+// returns the rows this workgroup rendered
+__device__ __noinline__ int rv_pc_tail(const ObsSnap* snaps_, float* out_, int* done_, int* claimed_, uint8_t* rendered_, int* count_,
+                                       const rv_config* cfg_, const rv_scene* scene_, int n_envs_, int n_steps_, int cap_, int env_, int tag_) {
+  __shared__ uint32_t s_key[RV_PC_MAXPIX];
+  static_assert(sizeof(Shared) >= (2 * RV_PC_MAXPIX + RV_MAXB * 9) * 4, "the env block is lent to the renderer: pixels, depths, rotations");
+  uint32_t* const s_pix = reinterpret_cast<uint32_t*>(&g_shared);
+  float* const s_dep = reinterpret_cast<float*>(&g_shared) + RV_PC_MAXPIX;
+  float (*const s_rot)[9] = reinterpret_cast<float (*)[9]>(reinterpret_cast<float*>(&g_shared) + 2 * RV_PC_MAXPIX);
+  const ObsSnap* const snaps = rv_uni_ptr(snaps_); float* const out = rv_uni_ptr(out_);
+  RV_GLOBAL int* const done = rv_uni_gptr(done_); RV_GLOBAL int* const claimed = rv_uni_gptr(claimed_);
+  RV_GLOBAL uint8_t* const rendered = rv_uni_gptr(rendered_);
+  const rv_config* const cfg = rv_uni_ptr(cfg_); const rv_scene* const scene = rv_uni_ptr(scene_);
+  const int n_envs = __builtin_amdgcn_readfirstlane(n_envs_), cap = __builtin_amdgcn_readfirstlane(cap_);
+  const int env = __builtin_amdgcn_readfirstlane(env_), tag = __builtin_amdgcn_readfirstlane(tag_);
+  const int all_done = tag | __builtin_amdgcn_readfirstlane(n_steps_);      // what an env of this XCD publishes when it has left
+  const int lane = (int)threadIdx.x;
+  const size_t P3 = (size_t)__builtin_amdgcn_readfirstlane(cfg->num_points) * 3;
+  const int gid0 = __builtin_amdgcn_readfirstlane(cfg->env_id_offset);
+  const int r = env & 7, M = (n_envs - r + 7) >> 3, p0 = env >> 3;      // the candidates: r + 8 p, p = p0, p0 + 1, ... around the ring of M
+  const int leave = RV_PC_TAIL_LEAVE < (M >> 3) ? RV_PC_TAIL_LEAVE : (M >> 3);
+  int n_done = 0;
+  while (n_done < cap) {
+    // ONE look at every candidate: how many are still running, and the first row that is there (ring order from the own env)
+    int running = 0, jj = -1, k = 0;
+    for (int base = 0; base < M; base += 64) {
+      const int i = base + lane;
+      int j = 0, c = 0; bool avail = false, runs = false;
+      if (i < M) {
+        int p = p0 + i; if (p >= M) p -= M;
+        j = r + 8 * p;
+        const int d = __hip_atomic_load(done + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        runs = d != all_done;      // (an env of another XCD counts as running for ever: then this rule never fires, no more)
+        if ((d & (int)0xff000000) == tag) {
+          c = __hip_atomic_load(claimed + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          avail = c < (d & 0x00ffffff);
+        }
+      }
+      running += (int)__popcll(__ballot(runs));
+      const unsigned long long todo = __ballot(avail);
+      if (jj < 0 && todo != 0ull) {
+        const int l = (int)__builtin_ctzll(todo);
+        jj = __builtin_amdgcn_readlane(j, l); k = __builtin_amdgcn_readlane(c, l);
+      }
+    }
+    if (jj < 0 || running < leave) break;      // nothing is there, or the launch is about to end: the rest is rendered after it
+    int mine = 0;
+    if (lane == 0) {
+      int expect = k;
+      mine = __hip_atomic_compare_exchange_strong(claimed + jj, &expect, k + 1, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ? 1 : 0;
+    }
+    if (!__builtin_amdgcn_readfirstlane(mine)) continue;      // (another renderer took that row -- one of finitely many: look again)
+    ++n_done;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");      // (buffer_inv sc1, once per row, before the row is loaded)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const size_t row = (size_t)k * (size_t)n_envs + (size_t)jj;
+    for (int b = 0; b < RV_MAXB; ++b) {
+      point_cloud_render(snaps[row], b, out + (row * RV_MAXB + (size_t)b) * P3, (uint32_t)(gid0 + jj), cfg, scene, s_pix, s_dep, s_key, s_rot);
+      __syncthreads();      // (the next cloud writes the arrays this one read)
+    }
+    if (lane == 0) rendered[row] = (uint8_t)1;
+  }
+  if (lane == 0 && n_done > 0) __hip_atomic_fetch_add(rv_uni_gptr(count_), n_done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  return n_done;
+}
+#endif
 
 // TMODE = MODE_ROLLOUT: the single-launch rollout, a kernel of its own (it is the one bench.py times and the profiles
 // name); TMODE = -1: every other mode, picked at run time from args.mode -- the substep loop is inlined once per
@@ -197,6 +299,33 @@ __global__ __launch_bounds__(RV_ENV_THREADS) RV_ENV_OCCUPANCY_ATTR void k_env(En
     }
     const unsigned long long t_begin = queued ? __builtin_amdgcn_s_memtime() : 0ull;
     rv_env_task<TMODE>(args, MODE, env, S, K, k0, queued ? k0 + 1 : 0);      // (the ONE call site of the env program in this kernel)
+#if RV_ENV_PC_TAIL
+    if constexpr (TMODE == MODE_ROLLOUT) {
+      // (what the tail needs of the launch arguments is read here, not at the kernel's entry: rv_kernarg_at)
+#define RV_KARG(T, f) rv_kernarg_at<T>((int)offsetof(EnvKernelArgs, f))
+      int* const pc_done = RV_KARG(int*, pc_done);
+      if (pc_done != nullptr) {
+        // the env is back in HBM and every row of it is stored (the steps an env that is done did not take: zero rows, never
+        // published one by one): say so, then render what is there -- rv_pc_tail
+        __syncthreads();
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const int me = (int)blockIdx.x, tag = (rv_xcc_id() + 1) << 24;
+        if (lane == 0) __hip_atomic_store(pc_done + me, tag | RV_KARG(int, n_substeps), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#ifdef RV_PROFILE
+        const unsigned long long t_tail = __builtin_amdgcn_s_memtime();
+#endif
+        int n_tail = 0;
+        const int cap = RV_KARG(int, pc_cap);
+        if (cap > 0) n_tail = rv_pc_tail(RV_KARG(ObsSnap*, rec.snaps), RV_KARG(float*, pc_out), pc_done, RV_KARG(int*, pc_claimed), RV_KARG(uint8_t*, pc_rendered),
+                                         RV_KARG(int*, pc_count), RV_KARG(const rv_config*, cfg), RV_KARG(const rv_scene*, scene), RV_KARG(int, n_envs), RV_KARG(int, n_substeps), cap, me, tag);
+#ifdef RV_PROFILE      // slot 36: clocks this workgroup spent rendering after its env; slot 37: the rows it rendered (tools/prof_rollout.py)
+        if (lane == 0) { DevEnv* g = RV_KARG(DevEnv*, envs) + me; g->prof[36] += __builtin_amdgcn_s_memtime() - t_tail; g->prof[37] += (unsigned long long)n_tail; }
+#endif
+        (void)n_tail;
+      }
+#undef RV_KARG
+    }
+#endif
     if (!queued) return;
     __syncthreads();                                   // (the env's block is written: every lane's stores are issued)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // ... and acknowledged by the L2 of this XCD
@@ -295,6 +424,10 @@ __device__ __forceinline__ void rv_env_task(const EnvKernelArgs& args, const int
   pa.lin_thr = args.lin_thr; pa.ang_thr = args.ang_thr; pa.check_after = args.check_after; pa.min_stable = args.min_stable; pa.max_steps = args.max_steps;
   pa.first_index = args.first_index; pa.auto_reset = args.auto_reset; pa.rec = args.rec; pa.env = env; pa.n_envs = args.n_envs; pa.budget = args.budget;
   pa.k0 = k0; pa.k_stop = k_stop;
+  pa.pc_done_off = -1;
+#if RV_ENV_PC_TAIL
+  if constexpr (TMODE == MODE_ROLLOUT) pa.pc_done_off = (int)offsetof(EnvKernelArgs, pc_done);      // (k_env's one argument starts the segment)
+#endif
   // ONE call of the env program per kernel (it holds the only copy of the substep loop)
   const int resetting = MODE == MODE_PARTIAL && RV_UNI(S.e.in_step == 2);   // rv_set_auto_reset: a step begun on a finished episode -> env.reset()
   if (MODE == MODE_MACRO || MODE == MODE_SUB || MODE == MODE_WAIT || (MODE == MODE_PARTIAL && !resetting)) {

@@ -300,167 +300,26 @@ __global__ __launch_bounds__(64) void k_point_cloud(const ObsSnap* snaps, int n_
   __shared__ float s_dep[RV_PC_MAXPIX];
   __shared__ uint32_t s_key[RV_PC_MAXPIX];
   __shared__ float s_rot[RV_MAXB][9];
-  const int lane = (int)threadIdx.x;
   const int si = (int)blockIdx.x / RV_MAXB, b = (int)blockIdx.x % RV_MAXB;
   if (si >= n_snaps) return;
-  const ObsSnap& s = snaps[si];
-  const int P = c->num_points;
-  float* o = out + ((size_t)si * RV_MAXB + b) * (size_t)P * 3;
-  const uint32_t gid = (uint32_t)(c->env_id_offset + si % n_envs);
-  if (lane < RV_MAXB) { m3 m = qmat(ldq(s.pose[lane] + 3)); stm(s_rot[lane], m); }
-  __syncthreads();
-  int n = 0;
-  const v3 cam_o = cam_position(&s);
-  if (s.shape[b] >= 0 && !s.is_static[b]) {
-    // screen rectangle of the body
-    const rv_shape* sh = &scene->shapes[s.shape[b]];
-    float mu = 1e30f, xu = -1e30f, mv = 1e30f, xv = -1e30f, mz = 1e30f;
-    {
-      const int h = lane >> 4, i = lane & 15;
-      if (h < sh->n_hulls && i < sh->n_verts[h]) {
-        const float sc = s.scale[b];
-        v3 pw = add(ld3(s.pose[b]), mulv(s_rot[b], mk(sh->verts[h][i][0] * sc, sh->verts[h][i][1] * sc, sh->verts[h][i][2] * sc)));
-        float u, v, z;
-        project_vertex(&s, pw, &u, &v, &z);
-        mz = z;
-        if (z > c->cam_near) { mu = xu = u; mv = xv = v; }
-      }
-    }
-    mu = wave_min(mu); xu = wave_max(xu); mv = wave_min(mv); xv = wave_max(xv); mz = wave_min(mz);
-    if (mz > c->cam_near) {
-      const float W1 = (float)(c->cam_width - 1), H1 = (float)(c->cam_height - 1);
-      const int u0 = (int)fclampr(ffloorr(mu) - 1.0f, 0.0f, W1), u1 = (int)fclampr(ffloorr(xu) + 2.0f, 0.0f, W1);
-      const int v0 = (int)fclampr(ffloorr(mv) - 1.0f, 0.0f, H1), v1 = (int)fclampr(ffloorr(xv) + 2.0f, 0.0f, H1);
-      const int w = u1 - u0 + 1, hh = v1 - v0 + 1;
-      const int total = (xu < 0.0f || xv < 0.0f || mu > W1 || mv > H1) ? 0 : w * hh;
-      // which link boxes of the arm can cover a pixel of this rectangle at all?  (bounding sphere of the box
-      // projected as a disc, generously; the arm is off-stage when the envs observe, so the answer is
-      // almost always "none" and the pixels pay nothing for it)
-      unsigned arm_mask = 0u;
-      if (s.arm_on == 1) {
-        bool may = false;
-        if (lane < RV_NCOL) {
-          const rv_arm* arm = &scene->arm;
-          const float hx = arm->col_half[lane][0] + c->margin, hy = arm->col_half[lane][1] + c->margin, hz = arm->col_half[lane][2] + c->margin;
-          const float r = fsqrtr(hx * hx + hy * hy + hz * hz) * 1.01f + 1e-4f;
-          float uc, vc, zc;
-          project_vertex(&s, ld3(s.arm_c[lane]), &uc, &vc, &zc);
-          if (zc - r <= c->cam_near) may = zc + r > 0.0f;          // too close to bound its disc: keep it
-          else {
-            const float f = fmaxr(fabsr(s.cam_intrinsics[0]), fabsr(s.cam_intrinsics[1])) + fabsr(s.cam_intrinsics[4]);     // (this env's calibration: camera noise)
-            const float rp = r * f / (zc - r) * 1.05f + 2.0f;
-            may = !(uc + rp < (float)u0 || uc - rp > (float)u1 || vc + rp < (float)v0 || vc - rp > (float)v1);
-          }
-        }
-        arm_mask = (unsigned)(__ballot(may) & 0x3ffull);
-      }
-      // pass 0 keeps every visible pixel; a body with more than RV_PC_MAXPIX of them is cast again and `num` of every
-      // `den` visible pixels are kept, evenly spaced in scan order (rank r goes to slot r * num / den, the first rank of
-      // a slot stays), so that the sample covers the whole body: every stride-th pixel, or, where that would leave
-      // fewer pixels than num_points asks for (they are between RV_PC_MAXPIX / 2 and RV_PC_MAXPIX), RV_PC_MAXPIX of all
-      unsigned num = 1u, den = 1u; int kept = 0;
-      for (int pass = 0; pass < 2; ++pass) {
-        n = 0;
-        for (int base = 0; base < total; base += 64) {
-          const int idx = base + lane;
-          bool vis = false; float dep = 0.0f; int u = 0, v = 0;
-          if (idx < total) {
-            u = u0 + idx % w; v = v0 + idx / w;
-            v3 dw = cam_to_world_dir(&s, pixel_dir_cam(&s, (float)u, (float)v));
-            int who = render_pixel(c, scene, s, s_rot, cam_o, dw, &dep, nullptr, arm_mask);
-            vis = (who == b) && dep > c->cam_near && crop_ok(c, deproject(&s, cam_o, (float)u, (float)v, dep));
-          }
-          const unsigned long long bal = __ballot(vis);
-          const int rank = n + (int)__popcll(bal & ((1ull << lane) - 1ull));
-          int pos = rank; bool keep = true;
-          if (den > 1u) {
-            const unsigned long long rn = (unsigned long long)rank * num;
-            pos = (int)(rn / den);
-            keep = rn - (unsigned long long)pos * den < (unsigned long long)num;
-          }
-          if (vis && keep && pos < RV_PC_MAXPIX) { s_pix[pos] = ((uint32_t)v << 16) | (uint32_t)u; s_dep[pos] = dep; }
-          n += (int)__popcll(bal);
-        }
-        if (n <= RV_PC_MAXPIX) break;
-        if (pass == 0) {
-          const int stride = (n + RV_PC_MAXPIX - 1) / RV_PC_MAXPIX;
-          kept = (n + stride - 1) / stride;
-          if (kept >= P) den = (unsigned)stride;
-          else { num = (unsigned)RV_PC_MAXPIX; den = (unsigned)n; kept = RV_PC_MAXPIX; }
-        }
-      }
-      if (den > 1u) n = kept;
-    }
-  }
-  __syncthreads();
-  if (n == 0) {                                  // group_by_labels: zeros when the body has no pixel
-    for (int j = lane; j < P * 3; j += 64) o[j] = 0.0f;
-    return;
-  }
-  if (n < P) {                                   // downsample: with replacement iff fewer than num_points
-    for (int j = lane; j < P; j += 64) {
-      const uint32_t i = pc_hash(c, gid, s.rng_arg, RV_PC_DRAW_CTR(b, j)) % (uint32_t)n;
-      const uint32_t px = s_pix[i];
-      st3(o + 3 * j, deproject(&s, cam_o, (float)(px & 0xffffu), (float)(px >> 16), s_dep[i]));
-    }
-    return;
-  }
-  // uniformly random P-subset: the P smallest keys.  Radix select of the P-th smallest key T
-  for (int i = lane; i < n; i += 64) s_key[i] = pc_hash(c, gid, s.rng_arg, RV_PC_KEY_CTR(b, i));
-  __syncthreads();
-  uint32_t prefix = 0u, mask = 0u; int k = P;
-  for (int bit = 31; bit >= 0; --bit) {
-    const uint32_t m2 = mask | (1u << bit);
-    int cnt = 0;
-    for (int base = 0; base < n; base += 64) {
-      const int i = base + lane;
-      const bool z = i < n && (s_key[i] & m2) == prefix;     // high bits match and this bit is 0
-      cnt += (int)__popcll(__ballot(z));
-    }
-    if (k > cnt) { k -= cnt; prefix |= (1u << bit); }
-    mask = m2;
-  }
-  const uint32_t T = prefix;       // k = how many keys equal to T are still needed (scan order)
-  // the selected pixels are compacted IN PLACE to the front of the three arrays (a lane writes at or below its own
-  // index, after every lane of the chunk has read its element) ...
-  int outn = 0, ties = 0;
-  for (int base = 0; base < n; base += 64) {
-    const int i = base + lane;
-    const uint32_t key = i < n ? s_key[i] : 0xffffffffu;
-    const uint32_t px = i < n ? s_pix[i] : 0u;
-    const float dp = i < n ? s_dep[i] : 0.0f;
-    const bool lt = i < n && key < T;
-    const bool eq = i < n && key == T;
-    const unsigned long long beq = __ballot(eq);
-    const int tie_rank = ties + (int)__popcll(beq & ((1ull << lane) - 1ull));
-    const bool sel = lt || (eq && tie_rank < k);
-    const unsigned long long bs = __ballot(sel);
-    const int pos = outn + (int)__popcll(bs & ((1ull << lane) - 1ull));
-    if (sel && pos < P) { s_key[pos] = key; s_pix[pos] = px; s_dep[pos] = dp; }
-    outn += (int)__popcll(bs); ties += (int)__popcll(beq);
-  }
-  __syncthreads();
-  // ... and go out in the order of their keys (ties in scan order): np.random.choice(replace=False) returns the
-  // subset in random order (point_cloud_utils.py:23-39).  Rank of an element = how many selected ones precede it;
-  // a lane ranks up to four elements per pass over the keys
-  for (int j0 = 0; j0 < P; j0 += 256) {
-    uint32_t kq[4]; int rq[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) { const int jj = j0 + lane + 64 * q; kq[q] = jj < P ? s_key[jj] : 0u; rq[q] = 0; }
-    for (int t = 0; t < P; ++t) {
-      const uint32_t kt = s_key[t];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) rq[q] += (kt < kq[q] || (kt == kq[q] && t < j0 + lane + 64 * q)) ? 1 : 0;
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int jj = j0 + lane + 64 * q;
-      if (jj < P) {
-        const uint32_t px = s_pix[jj];
-        st3(o + 3 * rq[q], deproject(&s, cam_o, (float)(px & 0xffffu), (float)(px >> 16), s_dep[jj]));
-      }
-    }
-  }
+  point_cloud_render(snaps[si], b, out + ((size_t)si * RV_MAXB + b) * (size_t)c->num_points * 3, (uint32_t)(c->env_id_offset + si % n_envs),
+                     c, scene, s_pix, s_dep, s_key, s_rot);
+}
+// ... behind a recorded rollout whose finished workgroups have rendered already (rv_env_kernel.h, "the tail"): rendered[si] = 1
+// marks their rows, whose blocks return at once; n_residual counts the rows rendered here.  (A kernel of its own: with the
+// flag test in it k_point_cloud compiled to other, slower code -- configs 3 and 5 spend 45 - 75 ms in that kernel.)
+__global__ __launch_bounds__(64) void k_point_cloud_rest(const ObsSnap* snaps, int n_snaps, int n_envs, float* out,
+                                                         const rv_config* c, const rv_scene* scene, const uint8_t* rendered, int* n_residual) {
+  __shared__ uint32_t s_pix[RV_PC_MAXPIX];
+  __shared__ float s_dep[RV_PC_MAXPIX];
+  __shared__ uint32_t s_key[RV_PC_MAXPIX];
+  __shared__ float s_rot[RV_MAXB][9];
+  const int si = (int)blockIdx.x / RV_MAXB, b = (int)blockIdx.x % RV_MAXB;
+  if (si >= n_snaps) return;
+  if (rendered[si]) return;
+  if (b == 0 && threadIdx.x == 0) atomicAdd(n_residual, 1);
+  point_cloud_render(snaps[si], b, out + ((size_t)si * RV_MAXB + b) * (size_t)c->num_points * 3, (uint32_t)(c->env_id_offset + si % n_envs),
+                     c, scene, s_pix, s_dep, s_key, s_rot);
 }
 // CameraObs 'depth' / 'segmask' (camera_obs.py:33-88 over BulletCamera._frames,
 // bullet_camera.py:188-235): the same ray cast as the point cloud, one thread per pixel.
@@ -602,6 +461,10 @@ struct rv_world {
   rv_macro_stats* d_stats;
   int* d_budget;
   ObsSnap* d_snaps; size_t n_snaps_cap;   // pose snapshots for the point-cloud render
+  // the words of the rollout kernel's tail (rv_env_kernel.h, rv_pc_tail; grown on demand, zeroed before every launch that
+  // uses them): [2] rows rendered by the tail / by the launch after it, [N] done, [N] claimed, then [n_steps x N] rendered
+  // bytes.  pc_rows: snapshot rows of the last recorded rollout (0: it took no point clouds), pc_flags: it used the words
+  int* d_pc_tail; size_t pc_tail_cap; size_t pc_rows; bool pc_flags;
   hipEvent_t ev0, ev1;
   bool timed;
   int auto_reset;                         // rv_set_auto_reset
@@ -693,10 +556,37 @@ static void poison_range(EnvKernelArgs& a) {
   const char* lo = getenv("RV_POISON_LO"); const char* hi = getenv("RV_POISON_HI");
   a.poison_lo = lo ? atoi(lo) : 0; a.poison_hi = hi ? atoi(hi) : 0x7fffffff;
 }
+// The tail of a recorded rollout (rv_env_kernel.h, rv_pc_tail): finished workgroups of the plain launch of the
+// register-rich kernel render point clouds; the k_point_cloud launch that follows renders the rows they left.
+// count[0] / count[1]: rows rendered by the tail / by that launch (rv_last_tail_renders)
+struct PcTail { int* count; int* done; int* claimed; uint8_t* rendered; float* out; int cap; };
+// RV_PC_TAIL (read per launch, as RV_QUEUE): 0 = off, the clouds are all rendered after the kernel; unset or 1 = on.
+// RV_PC_TAIL_CAP = n (a test aid that forces the mix): a finished workgroup renders n rows at most; 0 leaves every row
+// to the launch after the kernel.  Worlds on the two-waves-per-SIMD build have no tail
+static bool pc_tail_wanted(const rv_world* w, int n_steps) {
+  const char* t = getenv("RV_PC_TAIL");
+  return !(t && atoi(t) == 0) && !w->occ2 && n_steps < (1 << 24);
+}
+// the words of the tail for `rows` snapshot rows, zeroed on the world's stream
+static int pc_tail_setup(rv_world* w, size_t rows, float* d_out, PcTail* t) {
+  const size_t head = (size_t)(2 + 2 * (size_t)w->n) * sizeof(int), need = head + rows;
+  if (w->pc_tail_cap < need) {
+    if (w->d_pc_tail) { HIPCHK(hipStreamSynchronize(w->stream)); HIPCHK(hipFree(w->d_pc_tail)); w->d_pc_tail = nullptr; w->pc_tail_cap = 0; }
+    HIPCHK(hipMalloc(&w->d_pc_tail, need));
+    w->pc_tail_cap = need;
+  }
+  HIPCHK(hipMemsetAsync(w->d_pc_tail, 0, need, w->stream));
+  t->count = w->d_pc_tail; t->done = w->d_pc_tail + 2; t->claimed = t->done + w->n;
+  t->rendered = reinterpret_cast<uint8_t*>(w->d_pc_tail) + head; t->out = d_out;
+  const char* cap = getenv("RV_PC_TAIL_CAP");
+  t->cap = cap ? atoi(cap) : 0x7fffffff;
+  if (t->cap < 0) t->cap = 0;
+  return RV_OK;
+}
 template <int MODE>
 static int launch_env(rv_world* w, const uint8_t* mask, int n_sub, float lin, float ang, int ca, int ms, int mx,
                       int first_index = 0, int auto_reset = 0, const RolloutRec* rec = nullptr,
-                      int* budget = nullptr, int32_t* steps_taken = nullptr, long long pool_tasks = 0) {
+                      int* budget = nullptr, int32_t* steps_taken = nullptr, long long pool_tasks = 0, const PcTail* tail = nullptr) {
   EnvKernelArgs a;
   a.budget = budget; a.steps_taken = steps_taken; a.budget_clk = 0; a.finished = nullptr;
   a.first_index = first_index; a.auto_reset = auto_reset;
@@ -713,6 +603,10 @@ static int launch_env(rv_world* w, const uint8_t* mask, int n_sub, float lin, fl
     // workgroups that are resident first would use the pool up before the others have started
     int rc = queue_setup(w, 0, a, pool_tasks); if (rc != RV_OK) return rc;
     if (a.q_slots) { a.budget = nullptr; a.n_substeps = 0x7fffffff; }      // (an env always has "steps left": the pool ends the launch)
+  }
+  a.pc_done = nullptr; a.pc_claimed = nullptr; a.pc_rendered = nullptr; a.pc_count = nullptr; a.pc_out = nullptr; a.pc_cap = 0;
+  if (MODE == MODE_ROLLOUT && tail && a.q_slots == nullptr && !w->occ2 && a.rec.snaps) {      // (a queued launch has no tail: every row is left)
+    a.pc_done = tail->done; a.pc_claimed = tail->claimed; a.pc_rendered = tail->rendered; a.pc_count = tail->count; a.pc_out = tail->out; a.pc_cap = tail->cap;
   }
   HIPCHK(hipMemsetAsync(w->d_stats, 0, sizeof(rv_macro_stats), w->stream));
   HIPCHK(hipEventRecord(w->ev0, w->stream));
@@ -740,9 +634,12 @@ static int ensure_floats(rv_world* w, float** buf, size_t* cap, size_t n) {
   *cap = n;
   return RV_OK;
 }
-static int launch_point_cloud(rv_world* w, size_t n_snaps, float* d_out) {
-  hipLaunchKernelGGL(k_point_cloud, dim3((unsigned)(n_snaps * RV_MAXB)), dim3(64), 0, w->stream,
-                     w->d_snaps, (int)n_snaps, w->n, d_out, w->d_cfg, w->d_scene);
+// tail: the rows the rollout kernel's finished workgroups have rendered are flagged there and skipped here
+static int launch_point_cloud(rv_world* w, size_t n_snaps, float* d_out, const PcTail* tail = nullptr) {
+  if (tail) hipLaunchKernelGGL(k_point_cloud_rest, dim3((unsigned)(n_snaps * RV_MAXB)), dim3(64), 0, w->stream,
+                               w->d_snaps, (int)n_snaps, w->n, d_out, w->d_cfg, w->d_scene, (const uint8_t*)tail->rendered, tail->count + 1);
+  else hipLaunchKernelGGL(k_point_cloud, dim3((unsigned)(n_snaps * RV_MAXB)), dim3(64), 0, w->stream,
+                          w->d_snaps, (int)n_snaps, w->n, d_out, w->d_cfg, w->d_scene);
   HIPCHK(hipGetLastError());
   return RV_OK;
 }
@@ -842,6 +739,7 @@ int rv_create(const rv_config* cfg, const rv_scene* scene, int device, rv_world*
   if (!w) return fail(RV_ERR_STATE, "rv_create: out of host memory");
   w->cfg = *cfg; w->device = device; w->n = cfg->n_envs; w->stream = nullptr; w->timed = false;
   w->d_snaps = nullptr; w->n_snaps_cap = 0;
+  w->d_pc_tail = nullptr; w->pc_tail_cap = 0; w->pc_rows = 0; w->pc_flags = false;
   w->d_ap_depth = nullptr; w->ap_depth_cap = 0; w->d_ap_scratch = nullptr; w->ap_scratch_cap = 0;
   w->d_dn_scratch = nullptr; w->dn_scratch_cap = 0;
   w->d_route = nullptr;
@@ -890,6 +788,7 @@ int rv_destroy(rv_world* w) {
   (void)hipFree(w->d_cfg); (void)hipFree(w->d_scene);
   (void)hipFree(w->d_envs); (void)hipFree(w->d_stats); (void)hipFree(w->d_budget); if (w->d_q) (void)hipFree(w->d_q);
   if (w->d_snaps) (void)hipFree(w->d_snaps);
+  if (w->d_pc_tail) (void)hipFree(w->d_pc_tail);
   if (w->d_ap_depth) (void)hipFree(w->d_ap_depth);
   if (w->d_ap_scratch) (void)hipFree(w->d_ap_scratch);
   if (w->d_dn_scratch) (void)hipFree(w->d_dn_scratch);
@@ -933,10 +832,13 @@ int rv_rollout_record(rv_world* w, int32_t n_steps, int32_t first_macro_index, i
     int rc = ensure_snaps(w, rows); if (rc != RV_OK) return rc;
     rec.snaps = w->d_snaps;
   }
-  int rc = launch_env<MODE_ROLLOUT>(w, nullptr, n_steps, 0, 0, 0, 0, 0, first_macro_index, auto_reset, &rec);
+  PcTail tail; const bool use_tail = d_pc && pc_tail_wanted(w, n_steps);
+  if (use_tail) { int rc = pc_tail_setup(w, rows, d_pc, &tail); if (rc != RV_OK) return rc; }
+  w->pc_rows = d_pc ? rows : 0; w->pc_flags = use_tail;
+  int rc = launch_env<MODE_ROLLOUT>(w, nullptr, n_steps, 0, 0, 0, 0, 0, first_macro_index, auto_reset, &rec, nullptr, nullptr, 0, use_tail ? &tail : nullptr);
   if (rc != RV_OK) return rc;
-  // the segmented point clouds of all n_steps x N observations, rendered together
-  if (d_pc) return launch_point_cloud(w, rows, d_pc);
+  // the segmented point clouds of the n_steps x N observations: those the kernel's tail has not rendered, together
+  if (d_pc) return launch_point_cloud(w, rows, d_pc, use_tail ? &tail : nullptr);
   return RV_OK;
 }
 int rv_rollout_record_full(rv_world* w, int32_t n_steps, int32_t first_macro_index, int32_t auto_reset,
@@ -963,14 +865,28 @@ int rv_rollout_record_full(rv_world* w, int32_t n_steps, int32_t first_macro_ind
     }
   }
   if (extra && extra->d_reset) HIPCHK(hipMemsetAsync(extra->d_reset, 0, rows, w->stream));
-  int rc = launch_env<MODE_ROLLOUT>(w, nullptr, n_steps, 0, 0, 0, 0, 0, first_macro_index, auto_reset, &rec);
+  PcTail tail; const bool use_tail = d_pc && pc_tail_wanted(w, n_steps);
+  if (use_tail) { int rc = pc_tail_setup(w, rows, d_pc, &tail); if (rc != RV_OK) return rc; }
+  w->pc_rows = d_pc ? rows : 0; w->pc_flags = use_tail;
+  int rc = launch_env<MODE_ROLLOUT>(w, nullptr, n_steps, 0, 0, 0, 0, 0, first_macro_index, auto_reset, &rec, nullptr, nullptr, 0, use_tail ? &tail : nullptr);
   if (rc != RV_OK) return rc;
-  if (d_pc) { rc = launch_point_cloud(w, rows, d_pc); if (rc != RV_OK) return rc; }
-  if (d_rpc) {
+  if (d_pc) { rc = launch_point_cloud(w, rows, d_pc, use_tail ? &tail : nullptr); if (rc != RV_OK) return rc; }
+  if (d_rpc) {      // (the clouds after the resets: all of them here, as ever)
     hipLaunchKernelGGL(k_point_cloud, dim3((unsigned)(rows * RV_MAXB)), dim3(64), 0, w->stream,
                        w->d_snaps + rows, (int)rows, w->n, d_rpc, w->d_cfg, w->d_scene);
     HIPCHK(hipGetLastError());
   }
+  return RV_OK;
+}
+int rv_last_tail_renders(rv_world* w, int32_t* by_tail, int32_t* by_residual) {
+  WCHK(w);
+  if (!by_tail || !by_residual) return fail(RV_ERR_VALUE, "rv_last_tail_renders: null argument");
+  int32_t c[2] = {0, (int32_t)w->pc_rows};      // (no tail in that launch: every row was rendered after the kernel)
+  if (w->pc_flags) {
+    HIPCHK(hipMemcpyAsync(c, w->d_pc_tail, sizeof(c), hipMemcpyDeviceToHost, w->stream));
+    HIPCHK(hipStreamSynchronize(w->stream));
+  }
+  *by_tail = c[0]; *by_residual = c[1];
   return RV_OK;
 }
 int rv_rollout_async(rv_world* w, int32_t total_env_steps, int32_t first_macro_index, int32_t* d_steps_taken) {

@@ -46,6 +46,7 @@ SYMBOLS = [
     'rv_render_view',
     'rv_deproject', 'rv_segment_cloud',
     'rv_ward_workspace_bytes', 'rv_ward_groups',
+    'rv_last_tail_renders',
 ]
 
 _EXC = {abi.RV_ERR_VALUE: ValueError, abi.RV_ERR_STATE: RuntimeError,
@@ -191,7 +192,7 @@ def load():
     abi.bind_state_api(lib)
     for api in (abi.ANTIPODAL_API, abi.CEM_API, abi.DEPTH_NOISE_API, abi.PUSH_PROPOSAL_API, abi.PUSH_ROUTE_API,
                 abi.GRASP_CROP_API, abi.GRASP_QUALITY_API, abi.GRASP_TRAIN_API, abi.GRASP_REFINE_API, abi.VIEW_API,
-                abi.SEGMENT_API, abi.WARD_API):
+                abi.SEGMENT_API, abi.WARD_API, abi.PC_TAIL_API):
         for name, (res, args) in api.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, list(args)
@@ -556,6 +557,13 @@ class World(object):
         check(self.lib.rv_rollout_record_full(self.h, k, int(first_macro_index), int(bool(auto_reset)),
                                               self._ptr(r), self._ptr(d), C.byref(b), C.byref(ex)))
         return obs, r, d, {'actions': acts, 'reset': rst, 'reset_obs': robs}
+
+    def last_tail_renders(self):
+        """rv_last_tail_renders: (by_tail, by_residual) -- the snapshot rows of the last recorded rollout whose point
+        clouds the rollout kernel's finished workgroups rendered / the launch after the kernel rendered."""
+        a, b = C.c_int32(0), C.c_int32(0)
+        check(self.lib.rv_last_tail_renders(self.h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
 
     def rollout_async(self, total_env_steps, first_macro_index=0):
         """total_env_steps x (RandomPolicy action -> env.step) shared by all envs: every env

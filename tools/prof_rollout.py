@@ -35,6 +35,8 @@ ap.add_argument('--seed', type=int, default=1234)
 ap.add_argument('--over', nargs='*', default=[], help='config overrides, e.g. PHYSICS.SLEEP_STEPS=0')
 ap.add_argument('--top', type=int, default=6)
 ap.add_argument('--grasp', action='store_true', help='BASELINE config 4: Grasp4DofEnv (random CUBOID grasps)')
+ap.add_argument('--record', action='store_true', help='the measured launch records every step with point clouds, as bench.py does: '
+                'adds the slot "tail: point clouds" (what a workgroup renders after its env has finished, rv_env_kernel.h)')
 args = ap.parse_args()
 
 os.environ['RV_LIB'] = PROF_LIB
@@ -96,7 +98,10 @@ ws = args.steps if args.warm_steps is None else args.warm_steps
 for _ in range(args.warm):
     w.rollout(ws, first_macro_index=first, auto_reset=True, record=False); w.synchronize(); first += ws
 p0 = prof()
-w.rollout(args.steps, first_macro_index=first, auto_reset=True, record=False); w.synchronize()
+if args.record:
+    w.rollout_record(args.steps, first_macro_index=first, auto_reset=True, point_cloud=True); w.synchronize()
+else:
+    w.rollout(args.steps, first_macro_index=first, auto_reset=True, record=False); w.synchronize()
 ms = w.last_kernel_ms()
 p = prof() - p0
 st = w.stats()
@@ -135,4 +140,14 @@ print('coast loop counts, mean env / slowest env: substeps in the check-free pat
       % (p[:, 32].mean(), p[slow, 32], p[:, 33].mean(), p[slow, 33], p[:, 34].mean(), p[slow, 34], p[:, 35].mean(), p[slow, 35]))
 q = np.percentile(tot / clk * 1e3, [50, 90, 99, 100])
 print('env busy time ms: p50 %.1f  p90 %.1f  p99 %.1f  max %.1f' % tuple(q))
+if args.record:
+    # slot 36 / 37 (outside `main`: the time comes after the env's own, on a SIMD that would idle): clocks a workgroup spent
+    # rendering point clouds after its env, and the snapshot rows it rendered
+    by_tail, by_residual = w.last_tail_renders()
+    last = int(np.argmax(tot + p[:, 36]))
+    print('tail: point clouds -- rows rendered by the tail %d, by the launch after the kernel %d' % (by_tail, by_residual))
+    print('   %-40s %10s %10s %14s' % ('', 'mean env', 'slowest', 'last to leave'))
+    print('   %-40s %10.3f %10.3f %14.3f' % ('ms after the env\'s last step', p[:, 36].mean() / clk * 1e3, p[slow, 36] / clk * 1e3, p[last, 36] / clk * 1e3))
+    print('   %-40s %10.1f %10.0f %14.0f' % ('snapshot rows rendered', p[:, 37].mean(), p[slow, 37], p[last, 37]))
+    print('   env + tail, ms: slowest env %.1f, last workgroup to leave %.1f' % ((tot[slow] + p[slow, 36]) / clk * 1e3, (tot[last] + p[last, 36]) / clk * 1e3))
 w.close()
